@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s closest-hit, 1M-tri mesh, 1024^2 ray batch (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5i|c5ii]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5i|c5ii] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one `RayMeshIntersector.intersects_closest` call (the reference's timed call,
@@ -22,6 +22,13 @@ Workloads
   c5ii (BASELINE.json config 5): ONE batch of 100 000 000 hash rays (seed 99) split into N
        contiguous shards (triro.ray.sharded.shard_bounds), BVH replicated, results gathered to
        rank 0 INSIDE the timed region -> "scaling": "strong".
+
+A plain run sets up, warms up, times exactly `--steps` steps and prints the line (metric, value, unit,
+ms_per_step, config).  `--full` adds what takes runs or checks of its own: the `--warmup`-exactly protocol
+figure, the roofline (HIP event pairs), `verified` (last timed step == cold first call), the parity error
+bars, the companions (cold / first launch / moving camera / reference shape / pipelined / traversal; the
+other scaling for N > 1) and the CPU baseline.  `--dump-outputs DIR` writes the last timed step's outputs
+(rank 0's) as DIR/<name>.npy.
 
 `--gpus N` with N > 1 and no launcher environment: this process never touches the GPU; it checks
 that N devices are visible, starts N ranks with `python -m torch.distributed.run` (one per GPU,
@@ -94,8 +101,8 @@ def parse(argv=None):
                     help="test aid: run the N > 1 result pipeline (packed trace, RCCL exchange, expansion on a side stream, "
                          "double buffering) in a communicator of ONE rank -- what a single-GPU box can check of it; the line is labelled")
     ap.add_argument("--min-warmup-ms", type=float, default=50.0, help="keep warming up until this much time has passed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-companions", action="store_true", help="skip the cold / moving-camera / gather-ceiling companions")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-companions", action="store_true", help="--full: skip the cold / moving-camera / gather-ceiling companions")
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (tr_set_option)")
     ap.add_argument("--stats", action="store_true", help="also print traversal counters (diagnostic kernel)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -128,7 +135,43 @@ def parse(argv=None):
                          "preflight steps down from there (triro.ray.sharded.LADDER)")
     ap.add_argument("--no-preflight", action="store_true", help="N > 1: skip the checked small batch in front of the run")
     ap.add_argument("--stub", default=None, help="module:factory of a stand-in tracer (only with --backend gloo; tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (protocol figure, roofline, verified, "
+                         "parity, companions, CPU baseline); a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; a fixed seeded "
+                         "sample of the rays when they would exceed 64 MB, with ray_index.npy)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_NAMES = ("hit", "front", "tri_idx", "loc", "uv")
+
+
+def dump_outputs(path, out):
+    """intersects_closest's five outputs as path/<name>.npy: bool -> float32, integers -> float64 (exact), floats keep
+    their precision.  Above DUMP_BUDGET_BYTES a fixed sample of rays (seed 0, sorted) is written, with its indices."""
+    import numpy as np
+    import torch
+    if out is None or out[0] is None:
+        raise SystemExit("bench.py --dump-outputs: the timed path returned no outputs on this rank")
+    os.makedirs(path, exist_ok=True)
+    batch = tuple(out[0].shape)
+    n = out[0].numel()
+    flat = [x.reshape(n, *x.shape[len(batch):]) for x in out]
+    dts = [np.float32 if x.dtype == torch.bool else np.float64 if not x.dtype.is_floating_point else
+           (np.float64 if x.dtype == torch.float64 else np.float32) for x in flat]
+    per_ray = sum(np.dtype(dt).itemsize * (x[0].numel() if n else 1) for x, dt in zip(flat, dts))
+    idx = None
+    if n * per_ray + 1024 > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - 1024) // (per_ray + 8)   # (+ 8: the float64 index of each sampled ray; 1024: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        np.save(os.path.join(path, "ray_index.npy"), idx.astype(np.float64))
+        sel = torch.from_numpy(idx).to(flat[0].device)
+        flat = [x.index_select(0, sel) for x in flat]
+    for name, x, dt in zip(DUMP_NAMES, flat, dts):
+        a = x.cpu().numpy().astype(dt)
+        np.save(os.path.join(path, f"{name}.npy"), a if idx is not None else a.reshape(*batch, *a.shape[1:]))
 
 
 # ---- launcher --------------------------------------------------------------------------------
@@ -575,15 +618,16 @@ def run_rank(args):
 
     def timed_region(run, steps, warmup, min_warmup_ms, stride=None):
         """W untimed steps (and, when min_warmup_ms > 0, as many more as that much time takes), then EXACTLY `steps`
-        timed steps between barrier + synchronize on both sides; the time is the MAX over the ranks.  Sampled HIP event
-        pairs on the launch stream give the per-step GPU time."""
+        timed steps between barrier + synchronize on both sides; the time is the MAX over the ranks.  With --full,
+        sampled HIP event pairs on the launch stream give the per-step GPU time (the roofline's)."""
         import gc
         if stride is None:
             stride = max(1, int(args.event_stride)) if args.event_stride else max(1, steps // min(64, max(4, steps // 5)))
             if not args.event_stride and stride % 2 == 0:
                 stride += 1          # (odd: every 4th launch measures its block costs, the one behind it carries their sort -- the samples must not
                                      # lock onto either; a 20-step run keeps 4 pairs: a pair costs the wall clock ~5 us, 7 of them were 1 % of such a run)
-        ev = [event_pair() if k % stride == 0 else None for k in range(steps)]
+        # (a plain run has no event pairs: nothing but the steps between the clocks)
+        ev = [event_pair() if args.full and k % stride == 0 else None for k in range(steps)]
         gc.collect()
         gc.disable()            # a step is ~0.3 ms: keep collector pauses out of the timed region
         t_w = time.perf_counter()
@@ -668,8 +712,8 @@ def run_rank(args):
         out = run.drain()
     sync()
     first_call_ms = (time.perf_counter() - t_first) * 1e3
-    # what the cold call returned: the steady-state launches of the timed region must reproduce it bit for bit
-    first_out = [x.clone() for x in out] if out is not None and out[0] is not None else None
+    # what the cold call returned: the steady-state launches of the timed region must reproduce it bit for bit (--full)
+    first_out = [x.clone() for x in out] if args.full and out is not None and out[0] is not None else None
     # Everything that would leave the GPU idle between warm-up and the timed region (creating the
     # event objects, a garbage collection) happens BEFORE the warm-up: after a few milliseconds of
     # idleness the chip needs ~50 launches to come back to its steady clock, which is all a
@@ -681,22 +725,25 @@ def run_rank(args):
     # the library is still learning its launch order then (the first launches of a shape measure block costs and try
     # both node flavours), so this is what a caller gets on calls W+1 ... W+K of a new batch; `value` below is the
     # steady state after at least --min-warmup-ms of the same call.  Both are in the line (VERDICT r04 "next" #3).
+    # (a plain run times the steady state only: the protocol figure is --full's)
     proto = None
-    if args.min_warmup_ms > 0 and not stub:
+    if args.full and args.min_warmup_ms > 0 and not stub:
         proto = timed_region(run, args.steps, args.warmup, 0.0)
     main_ = timed_region(run, args.steps, args.warmup if proto is None else 0, args.min_warmup_ms)
     elapsed, kernel_ms, out = main_["elapsed"], main_["kernel_ms"], main_["out"] if main_["out"] is not None else out
     w_done = main_["warmup_done"] + ((proto["warmup_done"] + proto["steps"]) if proto else 0)
+    if args.dump_outputs and rank == 0:      # before anything else runs on this handle
+        dump_outputs(args.dump_outputs, out)
     # what an event pair costs with nothing between its two records: the interval a pair reports holds that much more
     # than the kernel (rocprofv3's dispatch time does not), which is how kernel_avg_ms could exceed ms_per_step
     empty_pair_ms = 0.0
-    if not stub:
+    if args.full and not stub:
         eps = timed_steps(200, lambda k: None)
         empty_pair_ms = float(np.median(eps))
-    if os.environ.get("TRIRO_BENCH_TRACE") and rank == 0:   # per-step durations, launch order
+    if os.environ.get("TRIRO_BENCH_TRACE") and rank == 0:   # per-step durations, launch order (--full: event pairs)
         print("per-step ms:", " ".join(f"{x:.3f}" for x in kernel_ms), file=sys.stderr)
-    kernel_raw_ms = float(np.mean(kernel_ms))
-    kernel_avg_ms = max(kernel_raw_ms - empty_pair_ms, 1e-6)
+    kernel_raw_ms = float(np.mean(kernel_ms)) if kernel_ms else None
+    kernel_avg_ms = max(kernel_raw_ms - empty_pair_ms, 1e-6) if kernel_ms else None
 
     # the last timed step against the cold first call (different launch order, split set, tiles and
     # node flavour; same rays): any difference is a bug in a "speed only" mechanism
@@ -706,7 +753,7 @@ def run_rank(args):
 
     # ---- N > 1: the other scaling of the same metric, in the same line (VERDICT r04 "next" #1b) -------------------
     companions_n = {}
-    if gather_on and world > 1 and not args.no_companions:
+    if args.full and gather_on and world > 1 and not args.no_companions:
         def companion(name, workload, scaling, chunks, steps):
             try:
                 w2 = build_workload(args, world, rank, dev, v, rad, resolve_share(args, world), workload, scaling, args.res, args.total_rays)
@@ -750,14 +797,11 @@ def run_rank(args):
         node_bytes_used = info["num_nodes"] * 32 if grid_nodes else info["node_bytes"]
         bvh_bytes = node_bytes_used + info["tri_bytes"]
         algo_bytes = n * BYTES_PER_RAY_CLOSEST + bvh_bytes          # per launch (= per rank and step)
-        achieved = algo_bytes / (kernel_avg_ms * 1e-3) / 1e9
-        algo_bytes_exact = n * BYTES_PER_RAY_CLOSEST + info["node_bytes"] + info["tri_bytes"]
-        compulsory = n * BYTES_PER_RAY_CLOSEST / (kernel_avg_ms * 1e-3) / 1e9
         traffic, traffic_src = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
         default_c5i = args.workload == "c5i" and args.res == 1024 and args.rays == "pinhole" and not strong_c5i
         default_c5ii = args.workload == "c5ii" and args.total_rays == C5II_RAYS
-        if (default_c5i or default_c5ii) and os.path.exists(tpath):
+        if args.full and (default_c5i or default_c5ii) and os.path.exists(tpath):
             try:
                 tj = json.load(open(tpath))
                 if default_c5i:
@@ -808,8 +852,6 @@ def run_rank(args):
             "metric": metric,
             "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "value_warmup_requested": round(n_total * proto["steps"] / proto["elapsed"] / 1e6, 2) if proto else None,
-            "ms_per_step_warmup_requested": round(proto["elapsed"] / proto["steps"] * 1e3, 4) if proto else None,
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
             "data": "stub tracer: launcher self-test, NOT a measurement" if stub else
                     ("synthetic; FUNCTIONAL RUN over gloo (ranks share GPUs, results staged through the host): NOT a measurement"
@@ -827,29 +869,35 @@ def run_rank(args):
                        "exchange": exchange,
                        "bvh_depth": info["depth"], "bvh_bytes": int(bvh_bytes), "bvh_build_ms": round(build_ms, 2),
                        "hit_fraction": round(float(hit0.float().mean().item()), 4) if hit0 is not None else None},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernel_name, "kernel_avg_ms": round(kernel_avg_ms, 4),
-                         "kernel_event_interval_ms": round(kernel_raw_ms, 4), "empty_event_pair_ms": round(empty_pair_ms, 4),
-                         "kernel_min_ms": round(max(kernel_ms[0] - empty_pair_ms, 0.0), 4),
-                         "kernel_median_ms": round(max(kernel_ms[len(kernel_ms) // 2] - empty_pair_ms, 0.0), 4), "kernel_samples": len(kernel_ms), "first_call_ms": round(first_call_ms, 4),
-                         "algorithmic_bytes": int(algo_bytes),
-                         "node_flavour": "32-byte grid nodes" if grid_nodes else "exact 64-byte nodes",
-                         "frac_on_exact_node_bytes": round(algo_bytes_exact / (kernel_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
-                         "compulsory_frac": round(compulsory / HBM_PEAK_GBPS, 5),
-                         "note": "achieved = (50 B/ray compulsory I/O + one read of the node and triangle arrays the launch walks) per launch / "
-                                 "kernel_avg_ms = the mean interval of kernel_samples HIP event pairs spread over the timed region "
-                                 "(kernel_event_interval_ms) minus what a pair reports with NOTHING between its records "
-                                 "(empty_event_pair_ms, the median of 200 measured in this run): the rocprofv3 dispatch time of "
-                                 "the same command is in profiles/r06c_summary.md; compulsory_frac counts the 50 B/ray only; the path is "
-                                 "cache-latency / instruction-issue bound, not HBM-bandwidth bound (DESIGN.md 5); "
-                                 "frac_on_exact_node_bytes = the same time against round 1's numerator (64-byte nodes), "
-                                 "for comparison across rounds only"},
         }
-        if gather_on:
-            res["roofline"]["note"] += ("; kernel_avg_ms here is the caller-stream time of a step (trace; the exchange and the "
-                                        "expansion run on RCCL's and a side stream)" if packed_ok else
-                                        "; kernel_avg_ms here includes the result gather")
+        if args.full:
+            res["value_warmup_requested"] = round(n_total * proto["steps"] / proto["elapsed"] / 1e6, 2) if proto else None
+            res["ms_per_step_warmup_requested"] = round(proto["elapsed"] / proto["steps"] * 1e3, 4) if proto else None
+            achieved = algo_bytes / (kernel_avg_ms * 1e-3) / 1e9
+            algo_bytes_exact = n * BYTES_PER_RAY_CLOSEST + info["node_bytes"] + info["tri_bytes"]
+            compulsory = n * BYTES_PER_RAY_CLOSEST / (kernel_avg_ms * 1e-3) / 1e9
+            res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": kernel_name, "kernel_avg_ms": round(kernel_avg_ms, 4),
+                               "kernel_event_interval_ms": round(kernel_raw_ms, 4), "empty_event_pair_ms": round(empty_pair_ms, 4),
+                               "kernel_min_ms": round(max(kernel_ms[0] - empty_pair_ms, 0.0), 4),
+                               "kernel_median_ms": round(max(kernel_ms[len(kernel_ms) // 2] - empty_pair_ms, 0.0), 4), "kernel_samples": len(kernel_ms), "first_call_ms": round(first_call_ms, 4),
+                               "algorithmic_bytes": int(algo_bytes),
+                               "node_flavour": "32-byte grid nodes" if grid_nodes else "exact 64-byte nodes",
+                               "frac_on_exact_node_bytes": round(algo_bytes_exact / (kernel_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
+                               "compulsory_frac": round(compulsory / HBM_PEAK_GBPS, 5),
+                               "note": "achieved = (50 B/ray compulsory I/O + one read of the node and triangle arrays the launch walks) per launch / "
+                                       "kernel_avg_ms = the mean interval of kernel_samples HIP event pairs spread over the timed region "
+                                       "(kernel_event_interval_ms) minus what a pair reports with NOTHING between its records "
+                                       "(empty_event_pair_ms, the median of 200 measured in this run): the rocprofv3 dispatch time of "
+                                       "the same command is in profiles/r06c_summary.md; compulsory_frac counts the 50 B/ray only; the path is "
+                                       "cache-latency / instruction-issue bound, not HBM-bandwidth bound (DESIGN.md 5); "
+                                       "frac_on_exact_node_bytes = the same time against round 1's numerator (64-byte nodes), "
+                                       "for comparison across rounds only"}
+            if gather_on:
+                res["roofline"]["note"] += ("; kernel_avg_ms here is the caller-stream time of a step (trace; the exchange and the "
+                                            "expansion run on RCCL's and a side stream)" if packed_ok else
+                                            "; kernel_avg_ms here includes the result gather")
         for name_, comp_ in companions_n.items():
             res[name_] = comp_
         if companions_n:
@@ -858,9 +906,10 @@ def run_rank(args):
                                    "work (strong_<res>: ONE res^2 batch cut into N row bands -- the metric's literal batch; weak: N such "
                                    "batches per step; default_chunks: the chunking ONE library call uses instead of bench.py's one chunk "
                                    "per shard with two steps in flight)")
-        res["parity"] = parity_error_bars()
+        if args.full:
+            res["parity"] = parity_error_bars()
         single = world == 1 and not stub
-        if single and not args.no_companions and args.workload == "c5i":
+        if args.full and single and not args.no_companions and args.workload == "c5i":
             # honest companions of the steady-state figure: the same launch
             # without a learned block order, and with an order that is always one frame stale
             rl = res["roofline"]
@@ -1008,7 +1057,7 @@ def run_rank(args):
         if args.stats and single:
             st = hops.trace_stats_closest(r.as_wrapper, origins, dirs)
             res["trace_stats"] = {k: (v_ / st["rays"] if k != "rays" else v_) for k, v_ in st.items()}
-        if single and not args.no_cpu_baseline:
+        if args.full and single and not args.no_cpu_baseline:
             if o_np is not None:
                 res["cpu_baseline"] = cpu_baseline(v, f, o_np, d_np)
             else:
@@ -1238,6 +1287,8 @@ def run_emulation(args):
         sync()
         rank0_ms = (time.perf_counter() - t0) / steps * 1e3
         m1 = device_mallocs()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     # the same without the peers (own shard only, dense): what the arrivals + expansions add
     for _ in range(warm):
         r.intersects_closest(o0, d0)

@@ -1,4 +1,4 @@
-python bench.py --no-cpu-baseline --no-companions 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read()); print('headline', r['value'], r['roofline']['kernel_avg_ms'])"
+python bench.py --full --no-cpu-baseline --no-companions 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read()); print('headline', r['value'], r['roofline']['kernel_avg_ms'])"
 python scripts/run_query.py --config c2 --query closest 2>/dev/null
 python scripts/run_query.py --config c4 --query closest 2>/dev/null
 python scripts/run_query.py --config c4 --query count 2>/dev/null

@@ -4,7 +4,7 @@ TAG=$1; shift
 mkdir -p gpurun_out
 : > gpurun_out/sweep_$TAG.log
 for A in "$@"; do
-  OUT=$(timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline $A 2>&1 | tail -1)
+  OUT=$(timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline $A 2>&1 | tail -1)
   echo "$A => $(echo "$OUT" | python3 -c "
 import sys,json
 try:

@@ -4,7 +4,7 @@ usage: python scripts/trace_steps.py [bench args]  -> prints mean kernel ms per 
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, TRIRO_BENCH_TRACE="1")
-p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-companions", *sys.argv[1:]],
+p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-companions", *sys.argv[1:]],
                    capture_output=True, text=True, env=env)
 for ln in p.stderr.splitlines():
     if ln.startswith("per-step ms:"):

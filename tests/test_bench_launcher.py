@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -14,12 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
-def run_bench(*args, timeout=240):
+def run_bench(*args, timeout=240, full=True):
+    """--full by default: these tests check `verified`, the companions and the parity block"""
     env = dict(os.environ)
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), env.get("PYTHONPATH", "")])
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
-    return subprocess.run([sys.executable, BENCH, *args], capture_output=True, text=True, timeout=timeout, env=env)
+    return subprocess.run([sys.executable, BENCH, *args, *(["--full"] if full else [])], capture_output=True, text=True,
+                          timeout=timeout, env=env)
 
 
 @pytest.mark.timeout(300)
@@ -136,3 +139,44 @@ def test_gpus2_refuses_when_fewer_devices_are_visible():
 def test_stub_is_rejected_with_the_real_backend():
     p = run_bench("--stub", "bench_stub:make", "--steps", "1")
     assert p.returncode != 0 and "only accepted with --backend gloo" in (p.stderr + p.stdout)
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """a plain run (no --full) prints the headline fields and nothing that takes runs of its own; --dump-outputs writes
+    the last timed step's outputs (float32 / float64, same shapes) and two runs with the same arguments write the same"""
+    common = ["--gpus", "2", "--backend", "gloo", "--stub", "bench_stub:make", "--subdiv", "2", "--res", "64",
+              "--steps", "3", "--warmup", "1", "--min-warmup-ms", "0"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = run_bench(*common, "--dump-outputs", str(d), full=False)
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = json.loads(p.stdout.strip().splitlines()[-1])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "Mrays/s"
+        assert r["higher_is_better"] is True and r["dtype"] == "f32" and r["metric"].startswith("Mrays/s closest-hit")
+        assert not any(k_ in r for k_ in ("roofline", "parity", "strong_64", "cpu_baseline", "value_warmup_requested"))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("hit", "front", "tri_idx", "loc", "uv")})
+    a, b = dumps
+    assert a["hit"].shape == (2 * 64, 64) and a["loc"].shape == (2 * 64, 64, 3) and a["uv"].shape == (2 * 64, 64, 2)
+    assert a["hit"].dtype == np.float32 and a["tri_idx"].dtype == np.float64 and a["loc"].dtype == np.float32
+    assert set(np.unique(a["hit"])) <= {0.0, 1.0} and np.array_equal(a["tri_idx"] >= 0, a["hit"] == 1)
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
+def test_dump_outputs_samples_large_outputs_within_budget(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40_000)
+    n = 5000
+    g = torch.Generator().manual_seed(1)
+    out = (torch.rand(n, generator=g) > 0.5, torch.rand(n, generator=g) > 0.5, torch.randint(-1, 1 << 20, (n,), dtype=torch.int32),
+           torch.rand(n, 3, generator=g), torch.rand(n, 2, generator=g))
+    bench.dump_outputs(str(tmp_path), out)
+    idx = np.load(tmp_path / "ray_index.npy").astype(np.int64)
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 40_000 and 0 < len(idx) < n
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "tri_idx.npy"), out[2].numpy()[idx].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "loc.npy"), out[3].numpy()[idx])
+    bench.dump_outputs(str(tmp_path / "again"), out)
+    assert np.array_equal(np.load(tmp_path / "again" / "ray_index.npy"), idx.astype(np.float64))

@@ -302,7 +302,7 @@ def test_bench_result_pipeline_on_rccl_one_rank():
                   ["--workload", "c5ii", "--total-rays", "7000001", "--chunks", "3", "--exchange", "native"]):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6",
-               "--warmup", "2", "--min-warmup-ms", "0", "--no-cpu-baseline", "--no-companions", "--force-gather"] + extra
+               "--warmup", "2", "--min-warmup-ms", "0", "--full", "--no-cpu-baseline", "--no-companions", "--force-gather"] + extra
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
         assert p.returncode == 0, (p.stdout[-800:], p.stderr[-2500:])
         line = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')][-1]

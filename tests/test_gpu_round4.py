@@ -22,7 +22,7 @@ def _port(base):
 
 
 def _bench(extra, timeout=900):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
