@@ -214,11 +214,14 @@ class OracleIntersector:
     def intersects_any(self, origins, directions):
         return self.intersects_count(origins, directions) > 0
 
-    def intersects_location(self, origins, directions, with_t=False):
+    def intersects_location(self, origins, directions, with_t=False, cap=MAX_ANYHIT_SIZE):
+        """`cap`: hits kept per ray (1..32, the C ABI's TR_MAX_HITS_CAP; the reference's fixed 8 by default)"""
+        if not 1 <= cap <= 32:
+            raise ValueError(f"cap {cap} outside [1, 32]")
         b, o, d = self._rays(origins, directions)
         n = len(o)
         cnt = self.intersects_count(o, d).reshape(-1)
-        clamped = np.minimum(cnt, MAX_ANYHIT_SIZE).astype(np.int64)  # ray.cpp:334-335
+        clamped = np.minimum(cnt, cap).astype(np.int64)              # ray.cpp:334-335
         incl = np.cumsum(clamped)                                    # ray.cpp:336
         nhits = int(incl[-1]) if n else 0                            # ray.cpp:339
         offsets = np.concatenate([[0], incl[:-1]]).astype(np.int64)  # ray.cpp:340-341
@@ -227,7 +230,7 @@ class OracleIntersector:
         tri = np.empty(nhits, np.int32)
         t = np.empty(nhits, np.float32)
         lib().oracle_location_fill(self._h, _p(o, C.c_float), _p(d, C.c_float), n, self.mode,
-                                   self.threads, MAX_ANYHIT_SIZE, _p(offsets, C.c_int64),
+                                   self.threads, int(cap), _p(offsets, C.c_int64),
                                    _p(loc, C.c_float), _p(ray, C.c_int32),
                                    _p(tri, C.c_int32), _p(t, C.c_float))
         if with_t:

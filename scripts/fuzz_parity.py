@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle parity sweep (run on the GPU box): random meshes, ray sets, ray tensor
-shapes and launch-shape options (work stealing thresholds, tiles, block sizes, adaptive order).
+shapes and launch-shape options (work stealing thresholds, tiles, node flavours, adaptive order).
 Every query must match the oracle bit for bit.  usage: python scripts/fuzz_parity.py [--iters 60] [--seed 1]"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,11 +16,11 @@ a = ap.parse_args()
 rng = np.random.default_rng(a.seed)
 dev = torch.device("cuda:0")
 T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-DEFAULTS = {"steal": 1, "tile": 1, "block_size": 128, "adaptive": 1, "xcd_chunk": 128, "compact": 1, "scramble": 1,
-            "persistent": 0, "blocks_per_cu": 8,
-            "tile_small": 4, "unordered": 1, "leaf_vote": 32, "stream": 1, "stream_rays": 256, "stream_refill": 0, "stream_dynamic": 1,
-            "split": 1, "split_steal": 8, "grid_nodes": 1, "split_outlier": 1, "split_floor": 40, "usteal": 1, "lds_top": 0, "occ8": 0,
-            "wide": 2, "wide_stack": 12, "wide_direct": 1, "expand4": 1, "expand_cus": 0, "expand_tiles": 1, "sort_inline": 1}
+# the initialisers of struct tr_options (csrc/tr_internal.h; tests/test_kernel_inventory.py checks this copy)
+DEFAULTS = {"adaptive": 1, "compact": 1, "xcd_chunk": 128, "steal": 1, "tile": 1, "tile_small": 4, "node_layout": 1,
+            "build_cache": 1, "stream": 1, "stream_rays": 256, "stream_refill": 0, "stream_dynamic": 1, "grid_nodes": 1,
+            "split": 1, "split_steal": 8, "split_outlier": 1, "split_floor": 40, "leaf_vote": 32, "order_transfer": 1,
+            "sort_inline": 1, "wide": 2, "wide_direct": 1, "wide_stack": 12, "expand_cus": 0, "expand_tiles": 1, "usteal": 1}
 bad = 0
 for it in range(a.iters):
     kind = rng.integers(0, 6)
@@ -86,12 +86,10 @@ for it in range(a.iters):
         n = int(rng.integers(64, 30000)); o, d = W.hash_rays(n, int(rng.integers(1 << 20)), lo - 0.1 * ext, hi + 0.1 * ext)
         d = ((lo + hi) / 2 - o + rng.normal(0, 0.05, o.shape) * ext).astype(np.float32)   # aimed at the mesh
     opts = {"steal": int(rng.choice([0, 1, 2, 5, 17, 64])), "tile": int(rng.choice([0, 1, 2])),
-            "block_size": int(rng.choice([64, 128, 128, 128, 128, 256])), "adaptive": int(rng.choice([0, 1, 1])),
-            "xcd_chunk": int(rng.choice([0, 16, 128, 300])), "compact": int(rng.choice([0, 1, 1])), "scramble": int(rng.choice([0, 1])),
-            # optional launch shape (persistent batches engage on batches larger than the resident grid)
-            "persistent": int(rng.choice([0, 0, 1])), "blocks_per_cu": int(rng.choice([1, 8])),
-            # unordered two-phase schedule of count / location (2: any as well) and its leaf-phase vote
-            "unordered": int(rng.choice([0, 1, 1, 2])), "leaf_vote": int(rng.choice([1, 4, 16, 48, 64])),
+            "adaptive": int(rng.choice([0, 1, 1])),
+            "xcd_chunk": int(rng.choice([0, 16, 128, 300])), "compact": int(rng.choice([0, 1, 1])),
+            # leaf-phase vote of the unordered two-phase schedule of count / location
+            "leaf_vote": int(rng.choice([1, 4, 16, 48, 64])),
             # streaming launch with wave-level ray refill (2 = forced at any size and shape)
             "tile_small": int(rng.choice([0, 1, 2, 3, 4])),
             "stream": int(rng.choice([0, 1, 2, 2])), "stream_rays": int(rng.choice([64, 100, 512, 4096])),
@@ -99,12 +97,12 @@ for it in range(a.iters):
             # block splitting of the stealing launch shapes (from the second launch of a batch on)
             "split": int(rng.choice([0, 1, 1, 2, 3, 4])), "split_steal": int(rng.choice([0, 2, 8, 64])),
             "grid_nodes": int(rng.choice([0, 1, 2, 2])),
-            # round 3: device-side split criterion, stealing in the unordered count launch, LDS-staged node packets
+            # round 3: device-side split criterion, stealing in the unordered count launch
             "split_outlier": int(rng.choice([0, 1, 1, 4, 8, 30])), "split_floor": int(rng.choice([0, 0, 0, 40])),
-            "usteal": int(rng.choice([0, 1, 1, 2, 8, 64])), "lds_top": int(rng.choice([0, 0, 1, 2])), "occ8": int(rng.choice([0, 1, 2, 2])),
-            # round 4: 8-wide compressed nodes (streaming launch, direct launch), their stack split, the expansion kernels
+            "usteal": int(rng.choice([0, 1, 1, 2, 8, 64])),
+            # round 4: 8-wide compressed nodes (streaming launch, direct launch), their stack split, the expansion launches
             "wide": int(rng.choice([0, 1, 1, 2])), "wide_stack": int(rng.choice([1, 2, 5, 12])), "wide_direct": int(rng.choice([0, 1, 2, 3, 3])),
-            "expand4": int(rng.choice([0, 1, 1, 2, 3])), "expand_cus": int(rng.choice([0, 0, 1, 3])), "expand_tiles": int(rng.choice([0, 1])),
+            "expand_cus": int(rng.choice([0, 0, 1, 3])), "expand_tiles": int(rng.choice([0, 1])),
             # round 5: the deferred sort of the learned order as a workgroup of the next launch
             "sort_inline": int(rng.choice([0, 1, 1, 1]))}
     for k, val in opts.items(): hops.set_option(k, val)

@@ -347,33 +347,27 @@ def test_stream_semantics(device):
 
 
 def test_launch_shapes_agree(device):
-    """persistent (work-counter) and direct launches return identical results"""
+    """the streaming (ray-refill) launch and the direct launch return identical results"""
     import triro.backend.ops as hops
+    from launch_options import options
     v, f = W.bunny_standin()
     r = make(v, f, device)
     o, d = W.hash_rays(3_000_000, 77, v.min(0) * 1.5, v.max(0) * 1.5)
     ot, dt = T(o, device), T(d, device)
-    try:
-        hops.set_option("persistent", 1)
+    with options(stream=2):
         a = r.intersects_closest(ot, dt)
         ca = r.intersects_count(ot, dt)
-        hops.set_option("persistent", 0)
+    with options(stream=0):
         b = r.intersects_closest(ot, dt)
         cb = r.intersects_count(ot, dt)
-    finally:
-        hops.set_option("persistent", 0)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     assert torch.equal(ca, cb)
     # every launch-shape knob of the direct kernel is a pure scheduling choice
-    defaults = {"adaptive": 1, "scramble": 1, "block_size": 128, "xcd_chunk": 128, "compact": 1, "steal": 1}
-    try:
-        for name, values in (("adaptive", (0,)), ("scramble", (0,)), ("block_size", (64, 256)),
-                             ("xcd_chunk", (0, 48, 1024)), ("compact", (0,)), ("steal", (0, 2, 8, 64))):
-            for val in values:
-                hops.set_option(name, val)
-                if name == "scramble":
-                    hops.set_option("adaptive", 0)        # the scrambled order is the one without hints
+    for name, values in (("adaptive", (0,)), ("split", (0, 3)), ("grid_nodes", (0, 2)),
+                         ("xcd_chunk", (0, 48, 1024)), ("compact", (0,)), ("steal", (0, 2, 8, 64))):
+        for val in values:
+            with options(stream=0, **{name: val}):
                 for _ in range(2):                        # second call runs on the learned order
                     c = r.intersects_closest(ot, dt)
                     for x, y in zip(c, b):
@@ -382,11 +376,6 @@ def test_launch_shapes_agree(device):
                     assert torch.equal(r.intersects_count(ot, dt), cb), (name, val)
                     assert torch.equal(r.intersects_first(ot, dt), b[2]), (name, val)
                     assert torch.equal(r.intersects_any(ot, dt), b[0]), (name, val)
-                hops.set_option(name, defaults[name])
-                hops.set_option("adaptive", 1)
-    finally:
-        for name, val in defaults.items():
-            hops.set_option(name, val)
     # size-independent properties at full size (10M-ray class inputs are covered in bench.py)
     hit, front, tri, loc, uv = a
     assert torch.equal(hit, tri >= 0) and torch.equal(hit, ca > 0)

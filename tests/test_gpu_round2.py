@@ -5,8 +5,9 @@
 * C-ABI hardening: face indices outside [0, nv) are reported, not dereferenced; queries refuse
   rays on another device; save/load after a shrinking update_raw; a failed build leaves an
   empty (not a dangling) handle; options may change while other threads query;
-* every launch shape reachable through tr_set_option (persistent work-counter launch; the
-  unordered two-phase schedule and its vote threshold) against the oracle.
+* every launch shape reachable through tr_set_option (the streaming launch on binary and 8-wide
+  nodes, the direct launch on 8-wide nodes; the unordered two-phase schedule with and without
+  hand-over between lanes, and its vote threshold) against the oracle.
 """
 import threading
 
@@ -15,6 +16,7 @@ import pytest
 import torch
 
 import workloads as W
+from launch_options import options, restore_defaults
 from oracle.oracle import OracleIntersector
 
 pytestmark = pytest.mark.gpu
@@ -236,7 +238,7 @@ def test_options_may_change_while_other_threads_query(device):
             k += 1
             hops.set_option("steal", (0, 1, 2, 8)[k % 4])
             hops.set_option("adaptive", k & 1)
-            hops.set_option("block_size", (64, 128, 256)[k % 3])
+            hops.set_option("grid_nodes", (0, 1, 2)[k % 3])
             hops.set_option("xcd_chunk", (0, 16, 128)[k % 3])
             hops.set_option("tile", k % 3)
 
@@ -250,40 +252,35 @@ def test_options_may_change_while_other_threads_query(device):
     finally:
         stop.set()
         th.join()
-        for k_, v_ in {"steal": 1, "adaptive": 1, "block_size": 128, "xcd_chunk": 128, "tile": 1}.items():
-            hops.set_option(k_, v_)
+        restore_defaults()
     with pytest.raises(ValueError):
         hops.set_option("stream_rays", 7)           # out of range
-    hops.set_option("block_size", 100)              # retired in round 5: accepted and ignored, like every retired name
-    hops.set_option("lds_top", 2)
+    for retired, value in (("block_size", 100), ("lds_top", 2)):     # retired in round 5: accepted and ignored, like every retired name
+        hops.set_option(retired, value)
     with pytest.raises(ValueError):
         hops.set_option("no_such_option", 1)
 
 
 SHAPES = [
-    {"persistent": 1},
-    {"persistent": 1, "blocks_per_cu": 2},
-    {"persistent": 1, "blocks_per_cu": 1, "block_size": 64},
+    dict(stream=2, wide=0),
+    dict(stream=2, wide=1),
+    dict(stream=0, wide_direct=3),
 ]
-SHAPE_DEFAULTS = {"persistent": 0, "blocks_per_cu": 8, "block_size": 128}
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: ",".join(f"{k}={v}" for k, v in s.items()))
 def test_optional_launch_shapes_match_the_oracle(device, shape):
     """every kernel reachable through tr_set_option is compared with the
-    oracle (not with another GPU launch): the persistent work-counter launch on a coherent and
-    an incoherent batch large enough for the persistent grid to engage.  (The per-lane refill
+    oracle (not with another GPU launch): the streaming launch forced on binary and on 8-wide nodes, and the direct
+    launch on 8-wide nodes for every query, on coherent and incoherent batches.  (The per-lane refill
     kernel of round 1 was deleted: the randomised sweep found a mismatch in it and it was 4x
     slower than the direct launch.)"""
-    import triro.backend.ops as hops
     cases = [
         (W.bunny_standin(), W.hash_rays(600_000, 31, [-1.6] * 3, [1.6] * 3)),
         (W.nested_shells(4), tuple(x.reshape(-1, 3) for x in W.pinhole_grid(800, 768))),
         (W.deep_tree_mesh(3000), W.hash_rays(530_000, 32, [-0.2] * 3, [1.2] * 3)),
     ]
-    try:
-        for k_, v_ in shape.items():
-            hops.set_option(k_, v_)
+    with options(**shape):
         for (v, f), (o, d) in cases:
             r = make(v, f, device)
             R = OracleIntersector(v, f, 1)
@@ -295,15 +292,13 @@ def test_optional_launch_shapes_match_the_oracle(device, shape):
             assert np.array_equal(r.intersects_first(ot, dt).cpu().numpy(), exp[2])
             assert np.array_equal(r.intersects_count(ot, dt).cpu().numpy(), cnt)
             assert np.array_equal(r.intersects_any(ot, dt).cpu().numpy(), cnt > 0)
-    finally:
-        for k_, v_ in SHAPE_DEFAULTS.items():
-            hops.set_option(k_, v_)
 
 
-@pytest.mark.parametrize("unordered,leaf_vote", [(0, 16), (1, 1), (1, 16), (1, 64), (2, 8), (2, 64)])
-def test_unordered_schedule_matches_the_oracle(device, unordered, leaf_vote):
+@pytest.mark.parametrize("usteal,leaf_vote", [(0, 16), (1, 1), (1, 16), (1, 64), (2, 8), (2, 64)])
+def test_unordered_schedule_matches_the_oracle(device, usteal, leaf_vote):
     """count / location / any through the unordered two-phase schedule (leaves queued in LDS, tested
-    in wave-voted leaf phases), every vote threshold from "always" to "only when forced", against
+    in wave-voted leaf phases) -- count without (usteal = 0) and with hand-over between lanes (1: from the
+    policy's trip, 2: forced from the second trip) --, every vote threshold from "always" to "only when forced", against
     the oracle: multi-layer scene with > 8 hits per ray (list replacement), incoherent rays on a
     soup, the deep tree (64-bit trail), image-shaped batches (8x8 tiles) and flat ones."""
     import triro.backend.ops as hops
@@ -313,9 +308,7 @@ def test_unordered_schedule_matches_the_oracle(device, unordered, leaf_vote):
         (W.deep_tree_mesh(3000), W.hash_rays(40_000, 42, [-0.2] * 3, [1.2] * 3)),
         (W.bunny_standin(), tuple(x.reshape(-1, 3) for x in W.pinhole_grid(320, 200))),
     ]
-    try:
-        hops.set_option("unordered", unordered)
-        hops.set_option("leaf_vote", leaf_vote)
+    with options(usteal=usteal, leaf_vote=leaf_vote):
         for (v, f), (o, d) in cases:
             r = make(v, f, device)
             R = OracleIntersector(v, f, 1)
@@ -327,9 +320,6 @@ def test_unordered_schedule_matches_the_oracle(device, unordered, leaf_vote):
             loc, ray, tri = [x.cpu().numpy() for x in r.intersects_location(ot, dt)]
             el, er, et = R.intersects_location(o, d)
             assert np.array_equal(ray, er) and np.array_equal(tri, et) and np.array_equal(loc, el)
-    finally:
-        hops.set_option("unordered", 1)
-        hops.set_option("leaf_vote", 32)
 
 
 @pytest.mark.parametrize("rays_per_wave,refill,dynamic", [(64, 1, 1), (100, 16, 1), (256, 32, 1), (512, 16, 0), (512, 64, 1),

@@ -10,11 +10,11 @@ import pytest
 import torch
 
 import workloads as W
+from launch_options import options
 from oracle.oracle import OracleIntersector
 
 pytestmark = pytest.mark.gpu
 LAUNCHES = 14
-OCC8_DEFAULT = 0       # the library's default of option occ8 (tests that flip it restore this)
 
 
 def T(x, dev):
@@ -217,30 +217,29 @@ def test_unordered_count_with_stealing_matches_the_oracle(device, usteal, split)
             hops.set_option(k, val)
 
 
-@pytest.mark.parametrize("lds_top", [1, 2, -8])
-def test_lds_staged_node_packets_match_the_oracle(device, lds_top):
-    """north_star "LDS-staged node packets" (option lds_top): closest / first launches that steal read the
-    grid nodes of the top 7 levels from a table staged in LDS while a wave descends them in lockstep.
+# variant -> options.  (The test was written for the LDS-staged table of the top levels and for eight waves per SIMD, two
+# launch variants that no longer exist; it keeps its name and its variant ids, and now runs the stealing launch on each
+# node flavour it can take.)
+NODE_VARIANTS = {
+    1: dict(grid_nodes=1),                               # the 32-byte grid nodes
+    2: dict(grid_nodes=0),                               # the exact 64-byte nodes
+    -8: dict(grid_nodes=2, steal=4, split_floor=0),      # grid nodes, stealing forced from the fourth trip, no time floor for split blocks
+}
+
+
+@pytest.mark.parametrize("variant", list(NODE_VARIANTS))
+def test_lds_staged_node_packets_match_the_oracle(device, variant):
+    """The node flavours of the stealing closest / first launches (option grid_nodes, NODE_VARIANTS).
     Image (tiles), flat, on-surface and hash batches, several launches each, a refit and a rebuild in
-    between (the table is derived data), a save / load round trip, and a mesh smaller than the table."""
-    import triro.backend.ops as hops
+    between (the grid nodes are derived data), a save / load round trip, and a mesh of a few dozen nodes."""
     from test_gpu_round2 import on_surface_rays
     from triro.ray.ray_optix import RayMeshIntersector
     v, f = W.icosphere(5)
     v = W.displaced(v, seed=4, amplitude=0.07)
     r = make(v, f, device)
     o_img, d_img = W.pinhole_grid(384, 256, distance=2.5)
-    # (lds_top = -8 stands for the OTHER variant of the stealing grid-node kernel this test covers: option
-    # occ8, 8 waves per SIMD with the slim ds_permute hand-over -- same batches, same launch sequence)
-    occ8 = lds_top < 0
-    lds_top = max(lds_top, 0)
-    try:
-        hops.set_option("lds_top", lds_top)
-        hops.set_option("occ8", 2 if occ8 else 0)
-        if occ8:
-            hops.set_option("grid_nodes", 2)
-            hops.set_option("steal", 4)
-            hops.set_option("split_floor", 0)
+    grid_nodes = NODE_VARIANTS[variant]["grid_nodes"]
+    with options(**NODE_VARIANTS[variant]):
         for step, (vv, how) in enumerate([(v, "build"), (W.displaced(v, seed=9, amplitude=0.03), "refit"), (v * np.float32(1.1), "update")]):
             if how == "refit":
                 r.refit(T(vv, device))
@@ -255,10 +254,10 @@ def test_lds_staged_node_packets_match_the_oracle(device, lds_top):
                 for rep in range(4):
                     got = [g.reshape((-1,) + tuple(g.shape[o.ndim - 1:])) for g in r.intersects_closest(ot, dt)]
                     for g, e in zip(got, exp[:5]):
-                        assert np.array_equal(g.cpu().numpy(), e), f"lds_top={lds_top} {how} {name} launch {rep}"
+                        assert np.array_equal(g.cpu().numpy(), e), f"variant {variant} (grid_nodes={grid_nodes}) {how} {name} launch {rep}"
                     assert np.array_equal(r.intersects_first(ot, dt).cpu().numpy().reshape(-1), exp[2])
             li = r.as_wrapper.last_launch()
-            assert li["grid_nodes"] == 1 and li["shape"] == 1
+            assert li["grid_nodes"] == (1 if grid_nodes else 0) and li["shape"] == 1
         import tempfile, os
         with tempfile.TemporaryDirectory() as td:
             r.save(os.path.join(td, "m"))
@@ -266,7 +265,7 @@ def test_lds_staged_node_packets_match_the_oracle(device, lds_top):
         a, b2 = r.intersects_closest(T(o_img, device), T(d_img, device)), r2.intersects_closest(T(o_img, device), T(d_img, device))
         for x, y in zip(a, b2):
             assert torch.equal(x, y)
-        # a mesh with fewer internal nodes than table slots
+        # a mesh of a few dozen nodes
         vs, fs = W.icosphere(1)
         rs, Rs = make(vs, fs, device), OracleIntersector(vs, fs, 1)
         os_, ds_ = W.pinhole_grid(128, 128, distance=3.0)
@@ -275,9 +274,6 @@ def test_lds_staged_node_packets_match_the_oracle(device, lds_top):
             got = rs.intersects_closest(T(os_, device), T(ds_, device))
             for g, e in zip(got, exp[:5]):
                 assert np.array_equal(g.cpu().numpy().reshape(e.shape), e)
-    finally:
-        for k_, v_ in (("lds_top", 0), ("occ8", OCC8_DEFAULT), ("grid_nodes", 1), ("steal", 1), ("split_floor", 40)):
-            hops.set_option(k_, v_)
 
 
 @pytest.mark.timeout(900)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import workloads as W
+from launch_options import options
 from oracle.oracle import OracleIntersector
 
 pytestmark = pytest.mark.gpu
@@ -84,7 +85,7 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo(extra):
     ["--emulate-world", "4", "--scaling", "strong", "--dst-share", "auto"],
     ["--emulate-world", "8", "--workload", "c5ii", "--total-rays", "2000003", "--dst-share", "auto", "--chunks", "2"],
     ["--emulate-world", "3", "--workload", "c5ii", "--total-rays", "500000", "--arrival-priority", "--records", "packed"],
-    ["--emulate-world", "8", "--arrival", "none", "--opt", "expand4=3"],
+    ["--emulate-world", "8", "--arrival", "none", "--opt", "expand_cus=3"],
 ], ids=["weak8", "weak8-even", "weak8-packed12", "strong4-weighted", "c5ii8-weighted", "c5ii3-priority", "weak8-no-arrival-tiles"])
 def test_emulated_destination_rank_is_bit_exact(extra):
     """bench.py --emulate-world: rank 0's step with N-1 chunks of records arriving as device copies and expanded on
@@ -98,7 +99,6 @@ def test_emulated_destination_rank_is_bit_exact(extra):
 def test_vectorised_expansion_matches_the_scalar_kernel_and_the_dense_trace(device):
     """tr_closest_expand: four rays per thread with 16-byte accesses (aligned rows) + the one-ray kernel for the
     rest; both == intersects_closest bit for bit, at every alignment of the row range"""
-    import triro.backend.ops as hops
     from triro.ray.ray_optix import RayMeshIntersector
     v, f = W.headline_mesh(5)
     r = RayMeshIntersector(vertices=torch.from_numpy(v).to(device), faces=torch.from_numpy(f).to(device))
@@ -110,9 +110,9 @@ def test_vectorised_expansion_matches_the_scalar_kernel_and_the_dense_trace(devi
     exp = r.intersects_closest(o, d)
     packed = r.intersects_closest_packed(o, d)
     assert 0.2 < float(exp[0].float().mean()) < 0.95
-    try:
-        for opt in (1, 0, 2, 3):
-            hops.set_option("expand4", opt)
+    # one workgroup per 1024 records (expand_cus = 0), or at most 1 / 3 / 64 workgroups per CU striding over the rest
+    for opt in (0, 1, 3, 64):
+        with options(expand_cus=opt):
             got = r.closest_expand(packed)
             for a, e in zip(got, exp):
                 assert torch.equal(a, e), opt
@@ -128,8 +128,6 @@ def test_vectorised_expansion_matches_the_scalar_kernel_and_the_dense_trace(devi
                     # nothing outside the range was written
                     assert int((outs[2][:lo] != -7).sum()) == 0 and int((outs[2][hi:] != -7).sum()) == 0
                     assert float((outs[3][:lo] != 9.0).sum()) == 0 and float((outs[3][hi:] != 9.0).sum()) == 0
-    finally:
-        hops.set_option("expand4", 1)
     # records that point outside the mesh (corrupt input) are misses, never out-of-bounds reads
     bad = packed.clone()
     bad[::7, 0] = 0x3fffffff

@@ -1,0 +1,199 @@
+"""Which test checks which kernel (CPU only).
+
+INVENTORY has one row per kernel of the gfx950 code object in libtriro_hip.so (demangled name, as
+scripts/code_object_notes.kernels() reads it).  A row names the GPU test(s) that launch the kernel deterministically and
+compare what it computes with the oracle or with an exact host computation -- or, as a string, why no such check
+exists.  A kernel added to the library without a row, or a row whose kernel is gone, fails here.
+
+The same module checks the options tests set: tests/launch_options.DEFAULTS against the initialisers of
+`struct tr_options`, and that no test or fuzz dimension sets an option the library only accepts and ignores."""
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "trimesh-ray-optix_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+# ---- the new flavour matrix (tests/test_gpu_kernel_matrix.py) -----------------------------------------------------------
+MATRIX = "test_gpu_kernel_matrix.py::test_flavour_matches_the_oracle"
+CAPS = "test_gpu_kernel_matrix.py::test_multi_hit_lists_match_the_oracle_at_every_cap"
+CAP_EDGES = "test_gpu_kernel_matrix.py::test_multi_hit_cap_range_and_ray_base"
+SCANS = "test_gpu_kernel_matrix.py::test_scans_match_an_int64_cumsum"
+COMPACTION = "test_gpu_kernel_matrix.py::test_compact_closest_with_a_ray_base"
+# ---- older tests ----------------------------------------------------------------------------------------------------------
+BUILDER = "test_gpu_parity.py::test_builder_invariants_and_host_traversal_of_gpu_tree"
+UPDATE = "test_gpu_parity.py::test_update_raw_rebuilds"
+REFIT = "test_gpu_parity.py::test_refit_and_serialization"
+PROBE = "test_gpu_round2.py::test_large_flat_batches_probe_and_both_launch_shapes"
+STEADY = "test_gpu_round3.py::test_c2_steady_state_launches_match_the_oracle"
+MOVING = "test_gpu_round3.py::test_c5i_moving_camera_sequence_matches_the_oracle"
+PACKED = "test_gpu_round3.py::test_packed_closest_expands_to_the_dense_outputs_bit_for_bit"
+PACKED_EDGES = "test_gpu_round3.py::test_packed_closest_edge_cases"
+SLOTS = "test_gpu_round4.py::test_slot_form_records_expand_to_the_dense_outputs"
+REPLICA = "test_gpu_round5.py::test_replica_hash_is_exact_and_stable"
+WIDE = "test_gpu_wide.py::test_wide_streaming_matches_the_oracle"
+
+STATS_ONLY = ("instrumented launch (tr_trace_stats_query): its query results go to internal scratch that is freed "
+              "unread, only the traversal counters come back -- there is nothing to compare with the oracle")
+
+INVENTORY = {}
+# k_query_direct<Q, STATS, COMPACT (32-bit offsets), MODE (0 plain, 1 stealing, 2 unordered), DEEP (64-bit trail), QN (grid nodes)>
+for q in (0, 1, 2):
+    for flags in ("false, false, 0, false, false", "false, false, 1, false, false",          # generic: plain, stealing
+                  "false, true, 0, false, false", "false, true, 0, true, false",             # compact / deep plain
+                  "false, true, 1, false, false", "false, true, 1, true, false",             # stealing on exact nodes
+                  "false, true, 1, false, true", "false, true, 1, true, true"):              # stealing on grid nodes
+        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX,)
+    INVENTORY[f"void k_query_direct<{q}, true, false, 0, false, false>"] = STATS_ONLY
+    # the stealing grid-node launch that carries the deferred sort of the learned order: <Q, DEEP, ...>
+    INVENTORY[f"void k_query_direct_sort<{q}, false, true, true>"] = (MATRIX,)
+    INVENTORY[f"void k_query_direct_sort<{q}, true, true, true>"] = (MATRIX,)
+for q in (3, 4):
+    for flags in ("false, false, 2, false, false", "false, true, 2, false, false", "false, true, 2, true, false"):
+        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX, CAPS) if q == 4 else (MATRIX,)
+    INVENTORY[f"void k_query_direct<{q}, true, false, 2, false, false>"] = STATS_ONLY
+# the stealing count launch <COMPACT, DEEP> and its sort-carrying form
+for flags in ("false, false", "true, false", "true, true"):
+    INVENTORY[f"void k_query_count_steal<{flags}>"] = (MATRIX,)
+INVENTORY["void k_query_count_steal_sort<false, true>"] = (MATRIX,)
+INVENTORY["void k_query_count_steal_sort<true, true>"] = (MATRIX,)
+for q in range(5):
+    INVENTORY[f"void k_query_direct_wide<{q}>"] = (MATRIX,)
+# streaming launches <Q, 32-bit offsets, block, DEEP> (no location query: it keeps the direct launch)
+for q in range(4):
+    for flags in ("false, 128, false", "true, 128, false", "true, 128, true"):
+        INVENTORY[f"void k_query_stream<{q}, {flags}>"] = (MATRIX,)
+    INVENTORY[f"void k_query_stream_stats<{q}, false, 128, false>"] = STATS_ONLY
+    INVENTORY[f"void k_query_wide<{q}>"] = (MATRIX, WIDE)
+INVENTORY.update({
+    # multi-hit lists: the two-pass fill (cap <= 8 / 16 / 32) and the fill from the fused traversal's slots
+    "void k_location<8>": (CAPS, CAP_EDGES),
+    "void k_location<16>": (CAPS,),
+    "void k_location<32>": (CAPS,),
+    "k_fill_list": (CAPS, CAP_EDGES, MATRIX),
+    "void k_scan_partial<int>": (SCANS, CAPS),
+    "void k_scan_final<int>": (SCANS, CAPS),
+    "void k_scan_partial<unsigned char>": (SCANS, COMPACTION),
+    "void k_scan_final<unsigned char>": (SCANS, COMPACTION),
+    "k_scan_partials": (SCANS,),
+    "k_compact_closest": (COMPACTION,),
+    # expansion of packed / slot records into the five dense outputs: bit-equal to the dense query
+    "void k_closest_expand<1>": (PACKED_EDGES,),
+    "void k_closest_expand_buf<4>": (PACKED,),
+    "void k_closest_expand_slots<1, false>": (SLOTS,),
+    "void k_closest_expand_slots<1, true>": (SLOTS,),
+    "void k_closest_expand_slots<4, false>": (SLOTS,),
+    "void k_closest_expand_slots<4, true>": (SLOTS,),
+    "void k_closest_expand_slots_tiled<false, false>": (SLOTS,),
+    "void k_closest_expand_slots_tiled<false, true>": (SLOTS,),
+    "void k_closest_expand_slots_tiled<true, false>": (SLOTS,),
+    "void k_closest_expand_slots_tiled<true, true>": (SLOTS,),
+    # the builder: its output is a hierarchy, checked structurally and by a host traversal against the oracle
+    "k_tri_bounds": (BUILDER,), "k_init_bounds": (BUILDER,), "k_morton": (BUILDER,), "k_rs_count": (BUILDER,),
+    "k_rs_scan": (BUILDER,), "k_rs_scatter": (BUILDER,), "void k_karras<0>": (BUILDER,), "void k_karras<1>": (BUILDER,),
+    "k_refit_round": (BUILDER, REFIT), "k_emit": (BUILDER,), "k_gather": (BUILDER,), "k_regather": (BUILDER, UPDATE),
+    "k_layout_init": (BUILDER,), "k_layout_round": (BUILDER,), "k_qframe": (BUILDER,), "k_qframe_box": (BUILDER,),
+    "k_refit_nodes_round": (REFIT,), "k_update_boxes": (REFIT,),
+    # the 8-wide nodes are built on first use by the launches that walk them
+    "k_wide_mark": (WIDE, MATRIX), "k_wide_emit": (WIDE, MATRIX),
+    "k_replica_hash": (REPLICA,),
+    # scheduling: these decide only the ORDER in which blocks run; the launches behind them are compared with the oracle
+    "k_probe_coherence": (PROBE,),
+    "k_sched_sort": (STEADY, MATRIX),
+    "k_sched_rescale": (MOVING,),
+})
+
+
+def _shipped_kernels():
+    import code_object_notes as con
+    so = os.path.join(ROOT, "trimesh-ray-optix_amd", "lib", "libtriro_hip.so")
+    if not os.path.exists(so) or not os.path.exists(con.READELF):
+        pytest.skip("library not built / llvm-readelf not available")
+    return {k["name"] for k in con.kernels(so)}
+
+
+def test_every_shipped_kernel_has_one_inventory_row():
+    names = _shipped_kernels()
+    missing = sorted(names - set(INVENTORY))
+    stale = sorted(set(INVENTORY) - names)
+    assert not missing, f"kernels in libtriro_hip.so without an inventory row: {missing}"
+    assert not stale, f"inventory rows of kernels that are not in libtriro_hip.so: {stale}"
+
+
+def test_inventory_rows_name_existing_tests_or_a_reason():
+    for kernel, row in INVENTORY.items():
+        if isinstance(row, str):
+            assert len(row) > 40, (kernel, row)
+            continue
+        assert row, kernel
+        for test_id in row:
+            module, func = test_id.split("::")
+            src = open(os.path.join(ROOT, "tests", module)).read()
+            assert re.search(rf"^def {func}\(", src, re.M), f"{kernel}: {test_id} does not exist"
+            assert "pytest.mark.gpu" in src, f"{kernel}: {test_id} is not a GPU test"
+    # the families the flavour matrix exists for: every 64-bit-addressing traversal kernel, the wide list kernels
+    # (<Q, STATS = false, COMPACT = false, ...> direct: plain and stealing for 3 queries + unordered for 2; streaming
+    # <Q, COMPACT = false, ...> for 4; the stealing count launch <COMPACT = false, DEEP = false>)
+    generic = [k for k in INVENTORY if re.match(r"void k_query_direct<\d, false, false,", k)
+               or re.match(r"void k_query_stream<\d, false,", k) or k == "void k_query_count_steal<false, false>"]
+    assert len(generic) == 3 * 2 + 2 + 4 + 1
+    for k in generic + ["void k_location<16>", "void k_location<32>"]:
+        assert isinstance(INVENTORY[k], tuple) and any(t.startswith("test_gpu_kernel_matrix.py") for t in INVENTORY[k]), k
+
+
+def _struct_tr_options():
+    src = open(os.path.join(CSRC, "tr_internal.h")).read()
+    body = re.search(r"struct tr_options \{(.*?)\n\};", src, re.S).group(1)
+    fields = re.findall(r"^\s*int (\w+) = (-?\d+);", body, re.M)
+    assert len(fields) == len(re.findall(r"^\s*int ", body, re.M)), "a field of tr_options without an integer initialiser"
+    return {k: int(v) for k, v in fields}
+
+
+def _fuzz_defaults():
+    """the DEFAULTS literal of scripts/fuzz_parity.py (a script: parsed, not imported)"""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, "scripts", "fuzz_parity.py")).read())
+    for node in tree.body:
+        if isinstance(node, ast.Assign) and any(getattr(t, "id", None) == "DEFAULTS" for t in node.targets):
+            return ast.literal_eval(node.value)
+    raise AssertionError("scripts/fuzz_parity.py has no DEFAULTS")
+
+
+def test_option_defaults_match_struct_tr_options():
+    from launch_options import DEFAULTS
+    assert DEFAULTS == _struct_tr_options()
+    # the fuzz script restores the same values after every iteration
+    assert _fuzz_defaults() == DEFAULTS
+    # ... and every field is an option tr_set_option knows by that name (csrc/api.hip's table)
+    api = open(os.path.join(CSRC, "api.hip")).read()
+    table = dict(re.findall(r'\{"(\w+)", &tr_options::(\w+),', api))
+    assert all(k == v for k, v in table.items()) and set(table) == set(DEFAULTS), table
+
+
+def _retired_names():
+    api = open(os.path.join(CSRC, "api.hip")).read()
+    lst = re.search(r"for \(const char\* retired : \{(.*?)\}\)", api, re.S).group(1)
+    names = re.findall(r'"(\w+)"', lst)
+    assert len(names) >= 13
+    return names
+
+
+def test_no_test_or_fuzz_dimension_sets_a_retired_option():
+    """A retired name is accepted and ignored by tr_set_option: a test that sets one claims coverage of a launch shape
+    that no longer exists.  Quoted option keys ('name' / "name") and keyword arguments (name=) are caught; the one
+    place allowed is the check that retired names are still accepted."""
+    names = _retired_names()
+    pat = re.compile(r"""(["'])(%s)\1|\b(%s)\s*=""" % ("|".join(names), "|".join(names)))
+    files = sorted(os.path.join(ROOT, "tests", f) for f in os.listdir(os.path.join(ROOT, "tests")) if f.endswith(".py"))
+    files.append(os.path.join(ROOT, "scripts", "fuzz_parity.py"))
+    hits = []
+    for path in files:
+        for n, line in enumerate(open(path), 1):
+            if pat.search(line):
+                hits.append((os.path.relpath(path, ROOT), n, line.strip()))
+    allowed = [h for h in hits if h[0] == os.path.join("tests", "test_gpu_round2.py") and h[2].startswith("for retired, value in (")]
+    assert len(allowed) == 1, hits
+    assert [h for h in hits if h not in allowed] == []
