@@ -197,3 +197,25 @@ def test_no_test_or_fuzz_dimension_sets_a_retired_option():
     allowed = [h for h in hits if h[0] == os.path.join("tests", "test_gpu_round2.py") and h[2].startswith("for retired, value in (")]
     assert len(allowed) == 1, hits
     assert [h for h in hits if h not in allowed] == []
+
+
+# the occupancy budgets (tests/test_round4_cpu.py pins them) and the branch hint of the open fault investigation
+# (scripts/round6/fault_probe.py builds with it)
+KEPT_SWITCHES = {"TR_DIRECT_WAVES", "TR_DEEP_WAVES", "TR_COUNT_WAVES", "TR_STREAM_WAVES", "TR_WIDE_WAVES", "TR_DRAIN_COLD"}
+
+
+def test_kernel_sources_keep_only_the_listed_build_switches():
+    """Every TR_ name the kernel sources test in the preprocessor (#ifdef / #ifndef / #if / #elif, defined(...)) is a
+    build switch: a `make EXTRA=-DTR_...` build swaps in another kernel.  The closed experiments' switches were retired
+    (experiments/README.md, "Retired build switches") so that the source shows exactly what ships, and so that a -D build
+    of a switch that stopped mattering cannot measure the default and report it as a variant.  A new switch has to be
+    added to KEPT_SWITCHES on purpose."""
+    directive = re.compile(r"^\s*#\s*(?:ifdef|ifndef|if|elif)\b(.*)$")
+    tested = {}
+    for f in sorted(os.listdir(CSRC)):
+        for n, line in enumerate(open(os.path.join(CSRC, f), errors="replace"), 1):
+            m = directive.match(line.split("//")[0])
+            if m:
+                for name in re.findall(r"\bTR_\w+", m.group(1)):
+                    tested.setdefault(name, []).append(f"{f}:{n}")
+    assert set(tested) == KEPT_SWITCHES, {k: v for k, v in tested.items() if k not in KEPT_SWITCHES}

@@ -12,17 +12,10 @@ template <> struct tr_word<true, false> { typedef uint32_t T; };
 // hierarchy is more than 32 levels high), 32-bit trail / owned words.  Chosen on the host per BVH.
 // COMPACT + DEEP is what meshes of a few million triangles and more get (5.2 M-triangle sphere: 34
 // levels): 80 instead of 82 VGPRs in the stealing closest kernel, i.e. 6 instead of 5 waves/SIMD.
-#ifndef TR_STREAM_QN
-#define TR_STREAM_QN true     // the streaming launch walks the 32-byte grid nodes (tr_rec_q)
-#endif
+constexpr bool TR_STREAM_QN = true;     // the streaming launch walks the 32-byte grid nodes (tr_rec_q)
 // the drain of parked leaf tests as a cold branch (tr_drain_exact): everywhere but in the streaming closest kernel on the
 // binary nodes, which answers the hint with ten spills (C3 closest +6 %: profiles/r06_ab_cold_drain.txt)
-#ifndef TR_STREAM_COLD
-#define TR_STREAM_COLD(Q) ((Q) != TR_Q_CLOSEST)
-#endif
-#ifndef TR_ALTERNATE
-#define TR_ALTERNATE 1        // every second trip runs without the leaf block (tr_fused_step<..., TEST>)
-#endif
+template <int Q> constexpr bool TR_STREAM_COLD = Q != TR_Q_CLOSEST;
 template <int Q, int K, bool STATS, bool COMPACT = false, bool UNI = false, bool DEEP = false>
 __device__ __forceinline__ void wave_traverse(const tr_bvh_view& b, tr_ray& r, bool go,
                                               tr_result& res, tr_topk<K>& top, tr_counters* cnt,
@@ -37,11 +30,8 @@ __device__ __forceinline__ void wave_traverse(const tr_bvh_view& b, tr_ray& r, b
     while (!tr_done(fs)) {
         tr_fused_step<Q, K, STATS, COMPACT, W, UNI, true>(b, r, fs, res, top, cnt, ring);
         TR_CONVERGE();
-#pragma unroll
-        for (int a = 0; a < TR_ALTERNATE; a++) {
-            tr_fused_step<Q, K, STATS, COMPACT, W, UNI, false>(b, r, fs, res, top, cnt, ring);   // no-op for a finished lane
-            TR_CONVERGE();
-        }
+        tr_fused_step<Q, K, STATS, COMPACT, W, UNI, false>(b, r, fs, res, top, cnt, ring);   // no-op for a finished lane
+        TR_CONVERGE();
     }
 }
 
@@ -57,18 +47,9 @@ __device__ __forceinline__ void wave_traverse(const tr_bvh_view& b, tr_ray& r, b
 // primary ray has normally found its hit (the thief inherits that bound), and what is left are
 // the grazing rays that make the long waves.  Splitting earlier costs culling (-6 % at 48, -15 %
 // at 32 on the headline).  wl = 6*64 ints of LDS scratch per wave.
-#ifndef TR_STEAL_EVERY
-#define TR_STEAL_EVERY 3u     // hand-overs are attempted on every (TR_STEAL_EVERY+1)-th trip ...
-#endif
-#ifndef TR_STEAL_SHARE
-#define TR_STEAL_SHARE 1      // lanes working on the same ray exchange their best hit at every look
-#endif
-#ifndef TR_STEAL_EARLY
-#define TR_STEAL_EARLY 4u       // ... and the trip from which a wave of UNRELATED rays gives subtrees away (wave_traverse_steal): its first look
-#endif
-#ifndef TR_STEAL_IDLE
-#define TR_STEAL_IDLE 1       // ... when at least this many lanes are idle
-#endif
+constexpr uint32_t TR_STEAL_EVERY = 3u;     // hand-overs are attempted on every (TR_STEAL_EVERY+1)-th trip ...
+constexpr uint32_t TR_STEAL_EARLY = 4u;     // ... and the trip from which a wave of UNRELATED rays gives subtrees away (wave_traverse_steal): its first look
+constexpr int TR_STEAL_IDLE = 1;            // ... when at least this many lanes are idle
 __device__ __forceinline__ int lane_rank(unsigned long long mask) {   // set bits of mask below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
@@ -115,9 +96,6 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             if (4 * __popcll(__ballot(go && alike)) < 3 * __popcll(act) && steal_min > TR_STEAL_EARLY) steal_min = TR_STEAL_EARLY;
         }
     }
-#ifdef TR_TIMELINE
-    int tl_handovers = 0;
-#endif
     // explicit LDS pointers: volatile accesses through generic pointers would compile to flat
     // loads/stores with 64-bit addresses held in VGPRs for the whole loop
     typedef __attribute__((address_space(3))) volatile int32_t lds_i32;
@@ -154,26 +132,17 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     };
     for (;;) {
         // TR_STEAL_EVERY+1 plain trips (idle lanes sit them out under the exec mask: a trip takes
-        // longer the more lanes take part in its loads), then one look at the wave
+        // longer the more lanes take part in its loads), in pairs of a trip with the leaf block and one
+        // without (tr_fused_step<..., TEST>), then one look at the wave
 #pragma unroll 1
-#if TR_ALTERNATE
-        for (uint32_t k = 0; k <= TR_STEAL_EVERY; k += 1 + TR_ALTERNATE) {
+        for (uint32_t k = 0; k <= TR_STEAL_EVERY; k += 2) {
             trip_step(std::true_type{});
             TR_CONVERGE();
-#pragma unroll
-            for (int a = 0; a < TR_ALTERNATE; a++) {
-                trip_step(std::false_type{});
-                TR_CONVERGE();
-            }
-        }
-#else
-        for (uint32_t k = 0; k <= TR_STEAL_EVERY; k++) {
-            if (!tr_done(fs)) tr_fused_step<Q, 1, STATS, COMPACT, W>(b, r, fs, res, top, cnt, ring);
+            trip_step(std::false_type{});
             TR_CONVERGE();
         }
-#endif
-        trip += TR_ALTERNATE ? (TR_STEAL_EVERY / (1u + TR_ALTERNATE) + 1u) * (1u + TR_ALTERNATE) : TR_STEAL_EVERY + 1u;
-        if (TR_STEAL_SHARE && split) {
+        trip += (TR_STEAL_EVERY / 2u + 1u) * 2u;
+        if (split) {
             // Rays that are traversed by several lanes share what they have found: a lane's bound is
             // the best hit of ANY lane working on its ray (closest / first), and an any-hit ray ends
             // for all of them with the first hit.  A bound that is a real hit of the same ray culls
@@ -183,12 +152,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             if (Q == TR_Q_ANY) {
                 if (res.best_face >= 0) vsum[owner] = 1;
                 __builtin_amdgcn_wave_barrier();
-                if (vsum[owner] != 0 && !tr_done(fs)) {
-                    fs.node = -1; fs.p0 = -1; fs.p1 = -1;
-#if TR_LEAF_QUEUE
-                    fs.p2 = -1;
-#endif
-                }
+                if (vsum[owner] != 0 && !tr_done(fs)) { fs.node = -1; fs.p0 = -1; fs.p1 = -1; fs.p2 = -1; }
             } else if (Q == TR_Q_CLOSEST || Q == TR_Q_FIRST) {
                 const bool have = res.best_slot >= 0;
                 const unsigned long long mine = ((unsigned long long)(__float_as_uint(res.best_t) & 0x7fffffffu) << 32) |
@@ -214,9 +178,6 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             const int ni = __popcll(idle), nd = __popcll(donors);
             const int np = ni < nd ? ni : nd;
             if (np > 0) {
-#ifdef TR_TIMELINE
-                tl_handovers += np;
-#endif
                 if (!split) {   // first hand-over in this wave: set the accumulators up
                     if (Q == TR_Q_COUNT || Q == TR_Q_ANY) vsum[lane] = 0;
                     else vkeys[lane] = ~0ull;
@@ -285,10 +246,6 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             }
         }
     }
-#ifdef TR_TIMELINE
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) { lw[0] = (int32_t)trip; lw[1] = tl_handovers; }
-#endif
     return split;
 }
 
@@ -368,10 +325,6 @@ __device__ __forceinline__ void wave_traverse_unordered(const tr_bvh_view& b, tr
     }
 }
 
-#ifdef TR_USTEAL_DEBUG
-__device__ unsigned g_usteal_debug[4];
-#endif
-
 // ---- the unordered schedule with work stealing (count) --------------------------------------------
 // A count launch has no culling, but on a silhouette image the grazing rays are outliers here too
 // (headline image: bulk done at 377 us of 556), and a launch that leaves wave slots of the chip empty
@@ -433,9 +386,6 @@ __device__ __forceinline__ int wave_count_unordered_steal(const tr_bvh_view& b, 
         const bool done = tr_udone(st);
         const unsigned long long idle = __ballot(done);
         if (idle == ~0ull) break;
-#ifdef TR_USTEAL_DEBUG
-        if (trip > (1u << 16)) { if (lane == 0) atomicAdd(&g_usteal_debug[0], 1u); if (!done) atomicAdd(&g_usteal_debug[1], 1u); break; }
-#endif
         if (idle == 0ull) continue;
         const W cand = st.trail & st.owned;          // owed far children that are still in the ring
         const bool can_give = !done && cand != 0 && trip >= steal_min;
@@ -443,9 +393,6 @@ __device__ __forceinline__ int wave_count_unordered_steal(const tr_bvh_view& b, 
         const int ni = __popcll(idle), nd = __popcll(donors);
         const int np = ni < nd ? ni : nd;
         if (np == 0) continue;
-#ifdef TR_USTEAL_DEBUG
-        if (lane == 0) atomicAdd(&g_usteal_debug[2], (unsigned)np);
-#endif
         const int drank = lane_rank(donors), irank = lane_rank(idle);
         const bool give = can_give && drank < np;
         const bool take = done && irank < np;
@@ -531,11 +478,6 @@ __device__ __forceinline__ void process_ray_unordered(const tr_bvh_view& b, cons
 }
 
 #include "traverse_wide.inc"
-
-#ifdef TR_TIMELINE
-// experiment build only (not part of the ABI): TR_TIMELINE = number of wave records kept
-__device__ unsigned long long g_timeline[4 * TR_TIMELINE];
-#endif
 
 // Order the blocks of the last launch by measured cost, most expensive first: one workgroup,
 // counting sort on the cost quantised to 256 levels (max-reduce, LDS histogram, scan, scatter;
@@ -675,16 +617,6 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
     const unsigned slot_shift = JOB ? 8u : 0u;
     const unsigned bid = blockIdx.x - slot_shift;
     int64_t nblk = gridDim.x - slot_shift;
-#ifdef TR_LDS_PAD
-    // experiment (scripts/exp_lds_budget.sh): what would a per-workgroup LDS table of TR_LDS_PAD
-    // bytes (e.g. the top levels of the tree staged once per workgroup) cost in occupancy alone?
-    __shared__ volatile int32_t pad_lds[TR_LDS_PAD / 4];
-    pad_lds[threadIdx.x] = (int32_t)blockIdx.x;      // volatile: the allocation must survive
-#endif
-#ifdef TR_TIMELINE
-    // experiment (scripts/exp_timeline.py): per-wave start / end / placement of the launch
-    const unsigned long long tl_start = wall_clock64();
-#endif
     const unsigned long long t_start = cost ? wall_clock64() : 0ull;
     __shared__ int32_t ring_lds[MODE == 4 ? 1 : TR_RING * BS];
     const tr_ring ring = {ring_lds + threadIdx.x, BS};
@@ -763,9 +695,6 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
         i = ((ty << lgh) + (lane >> lgw)) * width + (tx << lgw) + (lane & ((1 << lgw) - 1));
     }
     tr_counters cnt = {0, 0, 0};
-#ifdef TR_TIMELINE
-    unsigned long long tl_extra = 0;
-#endif
     if (MODE == 4) {
         // 8-wide compressed nodes, one ray per lane (wave_traverse_wide): count / location / closest / first / any
         __shared__ int32_t wstack_lds[(TR_WNODES + TR_WLEAVES) * BS];
@@ -808,10 +737,6 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
         const uint32_t smin = parts_lg ? (uint32_t)steal_min >> 16 : (uint32_t)steal_min & 0xffffu;      // (bit 15: adaptive, wave_traverse_steal)
         process_ray_steal<Q, STATS, COMPACT, DEEP, QN>(b, rf, out, i, i < rf.n && mine, &cnt, ring,
                                                        steal_lds + (threadIdx.x >> 6) * SCR, smin);
-#ifdef TR_TIMELINE
-        tl_extra = (unsigned)(steal_lds[(threadIdx.x >> 6) * SCR] & 0xffff) |
-                   ((unsigned long long)(steal_lds[(threadIdx.x >> 6) * SCR + 1] & 0xffff) << 16);
-#endif
     } else {
         // the plain shape is what large coherent batches get (small ones steal, incoherent ones
         // stream): look for wave-uniform trips (tr_fused_step)
@@ -821,28 +746,10 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
         // 100 MHz ticks.  A split block records twice what it would have cost in one piece (roughly):
         // it has to stay among the expensive ones, or the split set alternates between two groups of
         // blocks from one measurement to the next (and every other group of launches has a long tail)
-#ifndef TR_SPLIT_STICKY
-#define TR_SPLIT_STICKY 1     // extra doubling of a split block's recorded cost (0: recorded as parts x its slots' time: r05_ab_split_sticky.txt)
-#endif
+        constexpr int TR_SPLIT_STICKY = 1;     // extra doubling of a split block's recorded cost (0: recorded as parts x its slots' time: r05_ab_split_sticky.txt)
         const unsigned long long dt = (wall_clock64() - t_start) << (parts_lg ? parts_lg + TR_SPLIT_STICKY : 0);
         atomicMax(&cost[blk], (uint32_t)(dt > 0x7ffffull ? 0x7ffffull : dt));
     }
-#ifdef TR_TIMELINE
-    if ((threadIdx.x & 63) == 0) {
-        const uint64_t w = (uint64_t)blockIdx.x * (BS / 64) + (threadIdx.x >> 6);
-        if (w < TR_TIMELINE) {
-            g_timeline[w * 4 + 0] = tl_start;
-            g_timeline[w * 4 + 1] = wall_clock64();
-            g_timeline[w * 4 + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) << 32) |
-                                    (unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_ID | XCC_ID
-            unsigned long long extra = 0;
-            if (MODE == 1) {   // trips of the wave | hand-overs (wave_traverse_steal)
-                extra = tl_extra;
-            }
-            g_timeline[w * 4 + 3] = (unsigned long long)blk | (extra << 32);
-        }
-    }
-#endif
     flush_stats<STATS>(cnt, stats);
 }
 

@@ -52,10 +52,6 @@ __device__ __forceinline__ void query_stream_body(const tr_bvh_view& b, const Ra
                                                   const int* __restrict__ sel,
                                                   unsigned long long* work) {
     if (sel && *sel != 1) return;      // dual launch: this is the shape for incoherent batches (id 1)
-#ifdef TR_TIMELINE
-    const unsigned long long tl_start = wall_clock64();
-    unsigned tl_trips = 0, tl_refills = 0;
-#endif
     typedef typename tr_word<COMPACT, DEEP>::T W;
     __shared__ int32_t ring_lds[TR_RING * BS];
     const tr_ring ring = {ring_lds + threadIdx.x, BS};
@@ -125,9 +121,6 @@ __device__ __forceinline__ void query_stream_body(const tr_bvh_view& b, const Ra
                 }
             }
             next += nidle;     // lanes past `end` took nothing; the cursor only has to reach `end`
-#ifdef TR_TIMELINE
-            tl_refills++;
-#endif
         }
         // trips until the next refill is due (or, once the range is used up, until all lanes are
         // done): a plain single-exit loop like the direct launch's, with a wave-uniform exit test
@@ -135,35 +128,24 @@ __device__ __forceinline__ void query_stream_body(const tr_bvh_view& b, const Ra
         int idle_now;
         do {
             if (busy) {
-                tr_fused_step<Q, 1, STATS, COMPACT, W, false, true, TR_STREAM_QN, TR_STREAM_COLD(Q)>(b, r, fs, res, top, &cnt, ring);
+                tr_fused_step<Q, 1, STATS, COMPACT, W, false, true, TR_STREAM_QN, TR_STREAM_COLD<Q>>(b, r, fs, res, top, &cnt, ring);
                 busy = !tr_done(fs);
             }
             TR_CONVERGE();
+            // the trip without the leaf block, as a loop of one trip: written without the loop, the first / closest
+            // instantiations compile to the same instructions in another order -- an unmeasured change
 #pragma unroll
-            for (int a = 0; a < TR_ALTERNATE; a++) {
+            for (int a = 0; a < 1; a++) {
                 if (busy) {
-                    tr_fused_step<Q, 1, STATS, COMPACT, W, false, false, TR_STREAM_QN, TR_STREAM_COLD(Q)>(b, r, fs, res, top, &cnt, ring);
+                    tr_fused_step<Q, 1, STATS, COMPACT, W, false, false, TR_STREAM_QN, TR_STREAM_COLD<Q>>(b, r, fs, res, top, &cnt, ring);
                     busy = !tr_done(fs);
                 }
                 TR_CONVERGE();
             }
             idle_now = __popcll(__ballot(!busy));
-#ifdef TR_TIMELINE
-            tl_trips++;
-#endif
         } while (idle_now < stop);
     }
     if (rid >= 0) write_result<Q>(b, out, rid, r, res);
-#ifdef TR_TIMELINE
-    if ((threadIdx.x & 63) == 0 && wave < TR_TIMELINE) {
-        g_timeline[wave * 4 + 0] = tl_start;
-        g_timeline[wave * 4 + 1] = wall_clock64();
-        g_timeline[wave * 4 + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) << 32) |
-                                   (unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11));
-        g_timeline[wave * 4 + 3] = (unsigned long long)(wave & 0x0fffffff) | ((unsigned long long)(tl_trips & 0xffff) << 32) |
-                                   ((unsigned long long)(tl_refills & 0xffff) << 48);
-    }
-#endif
     flush_stats<STATS>(cnt, stats);
 }
 // (Round 3 ran the compact instantiations at 8 waves per SIMD, 64 registers: -2...-7 %.  Round 4's sign-selected slab

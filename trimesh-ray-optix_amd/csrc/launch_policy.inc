@@ -77,9 +77,7 @@ int enter_bvh_device(const tr_bvh* bvh, const tr_rays* rays, tr_device_guard* gu
 // buf = cost[TR_SCHED_MAX] | order[TR_SCHED_MAX] | stamp of the order (block count, split blocks,
 // 2 spare words) | 8 words of per-stream launch scratch (coherence-probe result, work counter)
 constexpr size_t TR_SCHED_WORDS = 4 * (size_t)TR_SCHED_MAX + 4 + 8 + 4;     // cost | order 0 | stamp | scratch | costs of the last sort | order 1 | stamp
-#ifndef TR_MEASURE_EVERY
-#define TR_MEASURE_EVERY 4          // (a power of two) steady state of a batch shape: every 4th launch measures its block costs
-#endif
+constexpr int64_t TR_MEASURE_EVERY = 4;     // (a power of two) steady state of a batch shape: every 4th launch measures its block costs
 constexpr int64_t TR_MEASURE_MASK = TR_MEASURE_EVERY - 1;
 constexpr size_t TR_SCHED_PREV = 2 * (size_t)TR_SCHED_MAX + 4 + 8;
 constexpr size_t TR_SCHED_ORDER1 = 3 * (size_t)TR_SCHED_MAX + 4 + 8;

@@ -24,14 +24,6 @@
 #include "tr_math.h"
 #include "../../include/triro_hip.h"   // tr_hit_entry
 
-// Leaf schedule of the fused trip.  1: ONE leaf test per trip out of a 3-slot per-lane FIFO (a
-// node visit can add two leaves while one is consumed; the node waits only when the FIFO is
-// full).  0: both leaves of the previous visit are tested in the same trip (two inlined tests,
-// 12 more live registers).  Results are identical; 1 is +5 % at >= 4 M rays, equal at 1 M.
-#ifndef TR_LEAF_QUEUE
-#define TR_LEAF_QUEUE 1
-#endif
-
 struct alignas(16) tr_f4 {
     float x, y, z, w;
 };
@@ -226,20 +218,14 @@ TR_HD void tr_qnode_set_box(uint32_t* q, const float* lo, const float* hi, const
     q[0] = lx | (ly << 16); q[1] = lz | (hz << 16); q[2] = hx | (hy << 16);
 }
 
-// TR_TRI_BYTES: 48 (packed: half of the records straddle a 64-byte line) or 64 (one line per record)
-#ifndef TR_TRI_BYTES
-#define TR_TRI_BYTES 48
-#endif
+// 48 bytes, packed: half of the records straddle a 64-byte line
 struct alignas(16) tr_tri {
     float ax, ay, az, bx, by, bz, cx, cy, cz;
     int32_t face;  // original triangle index
     float esum;    // tr_tri_scale: |b - a|_1 + |c - a|_1, the triangle's factor of the inside test's error bound (tr_tri_fast)
     int32_t pad1;
-#if TR_TRI_BYTES == 64
-    int32_t pad2[4];
-#endif
 };
-static_assert(sizeof(tr_tri) == TR_TRI_BYTES, "tri record must be 48 (or, experiment, 64) B");
+static_assert(sizeof(tr_tri) == 48, "tri record must be 48 B");
 
 struct tr_bvh_view {
     const tr_node* nodes;
@@ -261,10 +247,6 @@ enum tr_query { TR_Q_ANY = 0, TR_Q_FIRST = 1, TR_Q_CLOSEST = 2, TR_Q_COUNT = 3, 
 
 struct tr_counters {
     uint32_t nodes, tris, climbs;
-#ifdef TR_COUNT_BOTTOM
-    uint32_t bottom, bottom_hits;   // host experiment (scripts/exp_pair_leaves.py): visits of nodes whose
-                                    // children are both leaves, and how many of those passed the box test
-#endif
 };
 
 // sorted list of the K nearest hits (by (t, face)); static indexing only
@@ -414,9 +396,7 @@ TR_HD bool tr_fold_leaf(bool live, const tr_ray& r, const tr_tri& t, int32_t slo
     tr_hit h;
     h.t = 0.f;
     const int c = tr_tri_fast(r, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz, t.esum, h);
-#ifndef TR_NO_EXACT      // (-DTR_NO_EXACT: what the float64 part costs -- undecided tests count as misses: WRONG results, timing only)
     if (live && c == TR_UNDECIDED) pe = slot;
-#endif
     return tr_fold_hit<Q, K>(live && c == TR_HIT, h.t, t.face, slot, res, top);
 }
 // decide the parked test (see tr_fold_leaf); wave-uniform skip when no lane has one.
@@ -473,7 +453,7 @@ struct tr_ring {
 // then sent a 64-lane flat load through the texture addresser (the busiest unit of the kernels) and
 // waited for vmcnt AND lgkmcnt, where a ds_read_b32 would do.
 TR_HD int32_t tr_ring_get(const tr_ring& ring, uint32_t slot) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TR_RING_GENERIC)      // (-DTR_RING_GENERIC: the old code path, for A/B runs)
+#if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) int32_t tr_lds_i32;
     return ((tr_lds_i32*)ring.base)[slot * ring.stride];
 #else
@@ -481,7 +461,7 @@ TR_HD int32_t tr_ring_get(const tr_ring& ring, uint32_t slot) {
 #endif
 }
 TR_HD void tr_ring_put(const tr_ring& ring, uint32_t slot, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TR_RING_GENERIC)
+#if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) int32_t tr_lds_i32;
     ((tr_lds_i32*)ring.base)[slot * ring.stride] = v;
 #else
@@ -521,17 +501,13 @@ TR_HD bool tr_pending(const tr_state_t<W>& st) { return st.p0 >= 0 || st.p1 >= 0
 template <typename W>
 TR_HD bool tr_done(const tr_state_t<W>& st) { return st.node < 0 && st.p0 < 0 && st.p1 < 0 && st.pe < 0; }
 
-#ifndef TR_PK_SLAB
-#define TR_PK_SLAB 1
-#endif
-
 // Slab intervals of both children of a node held in three 16-byte registers:
 // n0 = lo0.x lo0.y lo0.z hi0.z | n1 = hi0.x hi0.y lo1.x lo1.y | n2 = lo1.z hi1.z hi1.x hi1.y.
 // On the device the 12 planes are packed FP32 (v_pk_add_f32 / v_pk_mul_f32: the same IEEE
 // subtract and multiply per plane as tr_slab, two planes per instruction).
 TR_HD void tr_node_slabs(const tr_ray& r, const tr_f4& n0, const tr_f4& n1, const tr_f4& n2,
                          float& tn0, float& tf0, float& tn1, float& tf1) {
-#if defined(__HIP_DEVICE_COMPILE__) && TR_PK_SLAB
+#if defined(__HIP_DEVICE_COMPILE__)
     typedef float tr_v2 __attribute__((ext_vector_type(2)));
     const tr_v2 oxy = {r.ox, r.oy}, ozz = {r.oz, r.oz};
     const tr_v2 ixy = {r.ix, r.iy}, izz = {r.iz, r.iz};
@@ -570,9 +546,6 @@ TR_HD void tr_node_step(const tr_bvh_view& b, const tr_ray& r, tr_state& st, con
     const float lim = tr_cull_limit<Q>(res);
     bool h0 = tr_slab_hit(tn0, tf0, lim);
     bool h1 = tr_slab_hit(tn1, tf1, lim);
-#ifdef TR_COUNT_BOTTOM
-    if (STATS && c0 < 0 && c1 < 0) { cnt->bottom++; cnt->bottom_hits += (h0 ? 1u : 0u) + (h1 ? 1u : 0u); }
-#endif
     // leaf children are queued for the leaf phase
     if (h0 && c0 < 0) { st.p0 = ~c0; h0 = false; }
     if (h1 && c1 < 0) { st.p1 = ~c1; h1 = false; }
@@ -643,83 +616,26 @@ TR_HD void tr_leaf_step(const tr_bvh_view& b, const tr_ray& r, tr_state& st, tr_
 // the triangle loads and the node loads are in flight together: one memory round trip per
 // trip.  Lanes never sit out.
 // Slab intervals of both children of a 32-byte grid node held in two 16-byte registers:
-// w0 = q[0..3], w1 = q[4], q[5], c0, c1.  Decode: plane = fma(q, scale, base) per 16-bit half; then
-// the contract's subtract and multiply per plane.  On the device both steps are packed FP32.
+// w0 = q[0..3], w1 = q[4], q[5], c0, c1.  The contract's form: plane = fma(q, scale, base) per 16-bit half, then
+// tr_slab's subtract and multiply per plane.  The kernels use the fused form below; tests/host_sim checks the two
+// against each other.
 TR_HD void tr_qnode_slabs_contract(const tr_ray& r, const tr_qframe& f, const tr_i4& w0, const tr_i4& w1,
                                    float& tn0, float& tf0, float& tn1, float& tf1) {
     const uint32_t q0 = (uint32_t)w0.x, q1 = (uint32_t)w0.y, q2 = (uint32_t)w0.z, q3 = (uint32_t)w0.w;
     const uint32_t q4 = (uint32_t)w1.x, q5 = (uint32_t)w1.y;
-#if defined(__HIP_DEVICE_COMPILE__) && TR_PK_SLAB && !defined(TR_QNOSIGN)
-    // Round 4: the planes the ray ENTERS a child box through and the ones it leaves through are selected per ray with
-    // three v_perm_b32 per child (selectors precomputed in tr_ray_setup), so that a child needs one max3 and one min3
-    // instead of six min / max before them: 21 instead of 24 instructions per child.  The values are tr_slab's -- min(t1,
-    // t2) IS the entry plane's t once the reciprocal's sign is known (rays are NaN-free) -- so nothing changes but the
-    // count: headline 0.205 -> 0.199 ms, C4 closest -3 %, terrain -5 %, count -2 % (-DTR_QNOSIGN: the old form, for A/B).
-    // It costs three registers: the 8-waves-per-SIMD variants (64 registers) no longer fit and were retired with it
-    // (streaming configs +-1 % at 7 waves: profiles/r04_ab_qsign.txt).
-    typedef float tr_v2 __attribute__((ext_vector_type(2)));
-    const tr_v2 sxy = {f.scale[0], f.scale[1]}, szz = {f.scale[2], f.scale[2]};
-    const tr_v2 bxy = {f.base[0], f.base[1]}, bzz = {f.base[2], f.base[2]};
-    const tr_v2 oxy = {r.ox, r.oy}, ozz = {r.oz, r.oz};
-    const tr_v2 ixy = {r.ix, r.iy}, izz = {r.iz, r.iz};
-#define TR_UNPK(w) tr_v2{(float)((w) & 0xffffu), (float)((w) >> 16)}
-    {
-        const uint32_t nxy = __builtin_amdgcn_perm(q2, q0, r.sel_n), fxy = __builtin_amdgcn_perm(q2, q0, r.sel_f);
-        const uint32_t zz = __builtin_amdgcn_perm(q1, q1, r.sel_z);      // (entry z | exit z << 16)
-        const tr_v2 a = (__builtin_elementwise_fma(TR_UNPK(nxy), sxy, bxy) - oxy) * ixy;
-        const tr_v2 c = (__builtin_elementwise_fma(TR_UNPK(fxy), sxy, bxy) - oxy) * ixy;
-        const tr_v2 b = (__builtin_elementwise_fma(TR_UNPK(zz), szz, bzz) - ozz) * izz;
-        tn0 = fmaxf(fmaxf(a.x, a.y), b.x);
-        tf0 = fminf(fminf(c.x, c.y), b.y) * TR_SLAB_PAD;
-    }
-    {
-        const uint32_t nxy = __builtin_amdgcn_perm(q5, q3, r.sel_n), fxy = __builtin_amdgcn_perm(q5, q3, r.sel_f);
-        const uint32_t zz = __builtin_amdgcn_perm(q4, q4, r.sel_z);
-        const tr_v2 a = (__builtin_elementwise_fma(TR_UNPK(nxy), sxy, bxy) - oxy) * ixy;
-        const tr_v2 c = (__builtin_elementwise_fma(TR_UNPK(fxy), sxy, bxy) - oxy) * ixy;
-        const tr_v2 b = (__builtin_elementwise_fma(TR_UNPK(zz), szz, bzz) - ozz) * izz;
-        tn1 = fmaxf(fmaxf(a.x, a.y), b.x);
-        tf1 = fminf(fminf(c.x, c.y), b.y) * TR_SLAB_PAD;
-    }
-#undef TR_UNPK
-#elif defined(__HIP_DEVICE_COMPILE__) && TR_PK_SLAB
-    typedef float tr_v2 __attribute__((ext_vector_type(2)));
-    const tr_v2 sxy = {f.scale[0], f.scale[1]}, szz = {f.scale[2], f.scale[2]};
-    const tr_v2 bxy = {f.base[0], f.base[1]}, bzz = {f.base[2], f.base[2]};
-    const tr_v2 oxy = {r.ox, r.oy}, ozz = {r.oz, r.oz};
-    const tr_v2 ixy = {r.ix, r.iy}, izz = {r.iz, r.iz};
-#define TR_UNPK(w) tr_v2{(float)((w) & 0xffffu), (float)((w) >> 16)}
-    const tr_v2 a = (__builtin_elementwise_fma(TR_UNPK(q0), sxy, bxy) - oxy) * ixy;   // child 0: x1 y1
-    const tr_v2 b = (__builtin_elementwise_fma(TR_UNPK(q1), szz, bzz) - ozz) * izz;   //          z1 z2
-    const tr_v2 c = (__builtin_elementwise_fma(TR_UNPK(q2), sxy, bxy) - oxy) * ixy;   //          x2 y2
-    const tr_v2 d = (__builtin_elementwise_fma(TR_UNPK(q3), sxy, bxy) - oxy) * ixy;   // child 1: x1 y1
-    const tr_v2 e = (__builtin_elementwise_fma(TR_UNPK(q4), szz, bzz) - ozz) * izz;   //          z1 z2
-    const tr_v2 g = (__builtin_elementwise_fma(TR_UNPK(q5), sxy, bxy) - oxy) * ixy;   //          x2 y2
-#undef TR_UNPK
-    tn0 = fmaxf(fmaxf(fminf(a.x, c.x), fminf(a.y, c.y)), fminf(b.x, b.y));
-    tf0 = fminf(fminf(fmaxf(a.x, c.x), fmaxf(a.y, c.y)), fmaxf(b.x, b.y)) * TR_SLAB_PAD;
-    tn1 = fmaxf(fmaxf(fminf(d.x, g.x), fminf(d.y, g.y)), fminf(e.x, e.y));
-    tf1 = fminf(fminf(fmaxf(d.x, g.x), fmaxf(d.y, g.y)), fmaxf(e.x, e.y)) * TR_SLAB_PAD;
-#else
     const float sx = f.scale[0], sy = f.scale[1], sz = f.scale[2], bx = f.base[0], by = f.base[1], bz = f.base[2];
     tr_slab(r, tr_qdecode(q0 & 0xffffu, sx, bx), tr_qdecode(q0 >> 16, sy, by), tr_qdecode(q1 & 0xffffu, sz, bz),
             tr_qdecode(q2 & 0xffffu, sx, bx), tr_qdecode(q2 >> 16, sy, by), tr_qdecode(q1 >> 16, sz, bz), tn0, tf0);
     tr_slab(r, tr_qdecode(q3 & 0xffffu, sx, bx), tr_qdecode(q3 >> 16, sy, by), tr_qdecode(q4 & 0xffffu, sz, bz),
             tr_qdecode(q5 & 0xffffu, sx, bx), tr_qdecode(q5 >> 16, sy, by), tr_qdecode(q4 >> 16, sz, bz), tn1, tf1);
-#endif
 }
 
 // The fused form (tr_ray_fuse): per child three v_perm_b32 (entry / exit planes of this ray), six conversions, THREE
 // packed fma, one max3, one min3 -- 14 instead of 22 instructions; no pad multiply (the margin e is in B).  Host and
 // device evaluate the same fma per plane: identical (tn, tf), so tests/host_sim walks the very path the kernels walk.
-#ifndef TR_QFUSE
-#define TR_QFUSE 1      // 0: the contract's three-step form (A/B builds)
-#endif
 TR_HD void tr_qnode_slabs(const tr_ray& r, const tr_qframe& f, const tr_i4& w0, const tr_i4& w1,
                           float& tn0, float& tf0, float& tn1, float& tf1) {
-#if !TR_QFUSE
-    tr_qnode_slabs_contract(r, f, w0, w1, tn0, tf0, tn1, tf1);
-#elif defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t q0 = (uint32_t)w0.x, q1 = (uint32_t)w0.y, q2 = (uint32_t)w0.z, q3 = (uint32_t)w0.w;
     const uint32_t q4 = (uint32_t)w1.x, q5 = (uint32_t)w1.y;
     typedef float tr_v2 __attribute__((ext_vector_type(2)));
@@ -805,9 +721,6 @@ TR_HD void tr_rec_links(const tr_rec_f& n, int32_t& parent, int32_t& sibling) {
 }
 TR_HD void tr_rec_links(const tr_rec_q&, int32_t& parent, int32_t& sibling) { parent = -1; sibling = -1; }
 
-#if !TR_LEAF_QUEUE
-#error "the fused trip needs the 3-slot leaf FIFO (TR_LEAF_QUEUE)"
-#endif
 // everything of a trip after the node record has arrived (n0..n3: in vector registers, or -- on
 // trips where the whole wave visits the same node -- in scalar registers)
 // TEST = false: a trip WITHOUT the leaf block (tr_fused_step)
@@ -835,7 +748,10 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
     const bool go = has_node && st.node >= 0;
     bool h0 = tr_slab_hit(tn0, tf0, lim) && go;
     bool h1 = tr_slab_hit(tn1, tf1, lim) && go;
-#if TR_LEAF_QUEUE
+    // Leaf schedule: ONE leaf test per trip out of a 3-slot per-lane FIFO (a node visit can add two
+    // leaves while one is consumed; the node waits only when the FIFO is full).  Testing both leaves
+    // of the previous visit in the same trip gives the same results with 12 more live registers and
+    // is 5 % slower at >= 4 M rays.
     // New FIFO = (carried entries, new leaf of child 0, new leaf of child 1), written as selects
     // (no shift-then-push: every move is a v_cndmask).  The head (p0) was consumed above; b =
     // old p1 and c = old p2 are carried.  When c is valid the node waited (go is false, no new
@@ -867,9 +783,6 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
         st.p1 = hb ? xi : (two ? i1 : -1);
         st.p2 = (hb && two) ? i1 : -1;
     }
-#else
-#error "unused"
-#endif
     if (go) {
         if (h0 || h1) {
             const bool both = h0 && h1;
@@ -992,9 +905,7 @@ TR_HD void tr_fused_step(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
 // bit-identical to the fused trip and to the oracle.  The triangle's own slab interval (the
 // [tn, tf] of the hit predicate) is recomputed from its vertices (tr_tri_hit: the same
 // tr_tri_box + tr_slab the builder stored in the parent), so the queue holds 4 bytes per leaf.
-#ifndef TR_LEAFQ
-#define TR_LEAFQ 6
-#endif
+constexpr int TR_LEAFQ = 6;
 struct tr_leafq {
     int32_t* base;
     int32_t stride;

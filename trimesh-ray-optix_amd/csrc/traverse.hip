@@ -42,28 +42,3 @@ void tr_wide_rebuild(tr_bvh* bvh, hipStream_t stream) {
 }
 
 #include "abi.inc"
-
-
-#ifdef TR_USTEAL_DEBUG
-extern "C" int tr_debug_usteal(unsigned* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_usteal_debug), 16);
-}
-#endif
-#ifdef TR_TIMELINE
-extern "C" int tr_debug_timeline(unsigned long long* host_out, long long n_waves) {
-    if (n_waves > TR_TIMELINE) n_waves = TR_TIMELINE;
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_timeline), (size_t)n_waves * 32);
-}
-#endif
-#ifdef TR_DEBUG_SCHED
-// experiment builds only (not part of the ABI): the scheduling buffer of (handle, stream, class) -> host
-extern "C" int tr_debug_sched(tr_bvh* bvh, void* stream, int cls, uint32_t* host_out, long long words) {
-    for (int k = 0; k < TR_SCHED_SLOTS; k++)
-        if (bvh->sched[k].used && bvh->sched[k].stream == (hipStream_t)stream && bvh->sched[k].cls == cls) {
-            (void)hipStreamSynchronize((hipStream_t)stream);
-            return (int)hipMemcpy(host_out, bvh->sched[k].buf, sizeof(uint32_t) * (size_t)words, hipMemcpyDeviceToHost);
-        }
-    return -1;
-}
-#endif
-

@@ -51,16 +51,12 @@ __global__ __launch_bounds__(256) void k_wide_emit(const tr_node* __restrict__ n
 // the <= 8 child boxes decoded and tested, hit leaves pushed, hit internal children pushed with the nearest of
 // them last (it is popped first).
 // Child box test: the planes a ray ENTERS through (lo where its direction is positive, hi where negative) and the
-// ones it leaves through are selected per ray before anything is decoded, so that a child costs 6 decodes, 6
-// subtract-multiplies, one max3 and one min3 -- the values are those of tr_slab on the decoded box (min(t1, t2) IS
-// the entry plane's t when the reciprocal's sign is known), pairs of children in packed FP32.
-#ifndef TR_WNODES
-#define TR_WNODES 12
-#endif
-#ifndef TR_WLEAVES
-#define TR_WLEAVES 12
-#endif
-#define TR_WSTACK TR_WNODES     // (host: LDS part of the node stack)
+// ones it leaves through are selected per ray before anything is decoded (min(t1, t2) IS the entry plane's t when the
+// reciprocal's sign is known), so that a child costs 6 conversions, 6 fma (the fused form below), one max3 and one
+// min3, pairs of children in packed FP32.
+constexpr int TR_WNODES = 12;
+constexpr int TR_WLEAVES = 12;
+constexpr int TR_WSTACK = TR_WNODES;     // (host: LDS part of the node stack)
 
 // one fused trip of one lane (all 64 lanes of the wave call it together): test one queued leaf, visit one node
 typedef __attribute__((address_space(3))) int32_t tr_wlds_i32;
@@ -96,11 +92,7 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
         if (STATS && is_node) cnt.nodes++;
         const uint32_t off = (uint32_t)item * (uint32_t)sizeof(tr_wnode);
         const tr_i4* p = reinterpret_cast<const tr_i4*>(reinterpret_cast<const char*>(wn) + off);
-#ifdef TR_WIDE_LATE_IDS
-        const tr_i4 h = p[0], q0 = p[1], q1 = p[2], q2 = p[3];
-#else
         const tr_i4 h = p[0], q0 = p[1], q1 = p[2], q2 = p[3], ia = p[4], ib = p[5];
-#endif
         const uint32_t ew = (uint32_t)h.w;
         const int nch = (int)(ew >> 24);
         const float lim = tr_cull_limit<Q>(res);
@@ -110,8 +102,7 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
         const bool ng[3] = {r.ix < 0.f, r.iy < 0.f, r.iz < 0.f};      // towards -x / -y / -z: the ray enters a box through its hi plane
         const float sc[3] = {tr_wscale(ew & 0xffu), tr_wscale((ew >> 8) & 0xffu), tr_wscale((ew >> 16) & 0xffu)};
         const float bs[3] = {__int_as_float(h.x), __int_as_float(h.y), __int_as_float(h.z)};
-        const float ro[3] = {r.ox, r.oy, r.oz}, ri[3] = {r.ix, r.iy, r.iz};
-#if TR_QFUSE
+        const float ro[3] = {r.ox, r.oy, r.oz};
         // Round 5, the fused conservative form (tr_ray_fuse, tr_bvh.h): the node's frame is folded into per-visit
         // constants -- A = scale * k, B = (base - o) * k -+ e: four instructions per axis -- and a plane costs ONE fma
         // instead of decode, subtract, multiply: 24 packed fma per visit instead of 72 packed instructions, no pad
@@ -121,11 +112,7 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
         float fA[3], fN[3], fF[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) tr_wfuse_axis(bs[k], sc[k], ro[k], rk[k], re[k], fA[k], fN[k], fF[k]);
-        (void)ri;
-#endif
-#ifndef TR_WIDE_LATE_IDS
         const int32_t ids[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
-#endif
         // the entry- and exit-plane dwords of the three axes (selected once per visit)
         uint32_t en[3][2], ex[3][2];
 #pragma unroll
@@ -135,11 +122,7 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
         uint32_t hits = 0;
         float near_t = INFINITY;
         int near_c = -1;
-#ifdef TR_WIDE_LATE_IDS
-        float tnv[8];
-#else
         int32_t near_id = -1;
-#endif
         // two children at a time (packed FP32), all three axes of the pair before the next pair: few live values
 #pragma unroll
         for (int pair = 0; pair < 4; pair++) {
@@ -149,15 +132,9 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
             for (int k = 0; k < 3; k++) {
                 const tr_v2 qn = {(float)((en[k][dw] >> sh) & 0xffu), (float)((en[k][dw] >> (sh + 8)) & 0xffu)};
                 const tr_v2 qx = {(float)((ex[k][dw] >> sh) & 0xffu), (float)((ex[k][dw] >> (sh + 8)) & 0xffu)};
-#if TR_QFUSE
                 const tr_v2 a2 = {fA[k], fA[k]}, n2 = {fN[k], fN[k]}, f2 = {fF[k], fF[k]};
                 const tr_v2 a = __builtin_elementwise_fma(qn, a2, n2);
                 const tr_v2 z = __builtin_elementwise_fma(qx, a2, f2);
-#else
-                const tr_v2 s2 = {sc[k], sc[k]}, b2 = {bs[k], bs[k]}, o2 = {ro[k], ro[k]}, i2 = {ri[k], ri[k]};
-                const tr_v2 a = (__builtin_elementwise_fma(qn, s2, b2) - o2) * i2;
-                const tr_v2 z = (__builtin_elementwise_fma(qx, s2, b2) - o2) * i2;
-#endif
                 tn2.x = fmaxf(tn2.x, a.x); tn2.y = fmaxf(tn2.y, a.y);
                 tf2.x = fminf(tf2.x, z.x); tf2.y = fminf(tf2.y, z.y);
             }
@@ -165,29 +142,12 @@ __device__ __forceinline__ void wide_trip(const tr_bvh_view& b, const tr_wnode* 
             for (int e = 0; e < 2; e++) {
                 const int c = 2 * pair + e;
                 const float tn = e ? tn2.y : tn2.x;
-#if TR_QFUSE
                 const float tf = e ? tf2.y : tf2.x;                      // (the exit margin is in fF)
-#else
-                const float tf = (e ? tf2.y : tf2.x) * TR_SLAB_PAD;
-#endif
                 const bool hc = tr_slab_hit(tn, tf, lim) && is_node && c < nch;
                 hits |= hc ? (1u << c) : 0u;
-#ifdef TR_WIDE_LATE_IDS
-                tnv[c] = tn;
-#else
                 if (hc && ids[c] >= 0 && tn < near_t) { near_t = tn; near_id = ids[c]; near_c = c; }
-#endif
             }
         }
-#ifdef TR_WIDE_LATE_IDS
-        // the child ids only now (the same line as the boxes: an L1 hit), into registers the boxes have left
-        const tr_i4 ia = p[4], ib = p[5];
-        const int32_t ids[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
-        int32_t near_id = -1;
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            if (((hits >> c) & 1u) && ids[c] >= 0 && tnv[c] < near_t) { near_t = tnv[c]; near_id = ids[c]; near_c = c; }
-#endif
         // hit leaves -> leaf stack; hit internal children -> node stack, the nearest of them last
 #pragma unroll
         for (int c = 0; c < 8; c++)
