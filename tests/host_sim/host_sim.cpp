@@ -357,6 +357,7 @@ void sim_set_qnodes(const void* qnodes, const float* f6) {
 void sim_use_ring(int on) { g_use_ring = on; }
 void sim_use_fused(int mode) { g_fused = mode; }
 void sim_use_unordered(int on) { g_unordered = on; }
+void sim_use_node_layout(int layout) { g_node_layout = layout; }   // read by sim_build: 0 = Karras numbering, 1 = treelets
 void sim_query(int q, const void* nodes, const void* links, const void* tris, int64_t nf, const float* o,
                const float* d, int64_t n, uint8_t* hit, uint8_t* front, int32_t* tri, float* loc, float* uv,
                int32_t* count, uint64_t* stats) {

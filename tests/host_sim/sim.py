@@ -37,6 +37,7 @@ def lib():
         L.sim_use_ring.argtypes = [C.c_int]
         L.sim_use_fused.argtypes = [C.c_int]
         L.sim_use_unordered.argtypes = [C.c_int]
+        L.sim_use_node_layout.argtypes = [C.c_int]
         L.sim_steps.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.sim_packet_stats.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.sim_check_fused_wide.restype = C.c_int64
@@ -181,3 +182,9 @@ def use_fused(mode: int):
 def use_unordered(on: bool):
     """any / count / location through the unordered two-phase schedule (queued leaves)"""
     lib().sim_use_unordered(1 if on else 0)
+
+
+def use_node_layout(layout: int):
+    """node order of the NEXT SimBVH builds, as the product's option node_layout: 0 = Karras numbering, 1 = treelet
+    order (the default)"""
+    lib().sim_use_node_layout(int(layout))

@@ -35,6 +35,14 @@ PACKED_EDGES = "test_gpu_round3.py::test_packed_closest_edge_cases"
 SLOTS = "test_gpu_round4.py::test_slot_form_records_expand_to_the_dense_outputs"
 REPLICA = "test_gpu_round5.py::test_replica_hash_is_exact_and_stable"
 WIDE = "test_gpu_wide.py::test_wide_streaming_matches_the_oracle"
+# ---- the builder matrix (tests/test_gpu_builder_matrix.py): downloaded arrays against numpy references ---------------------
+SIZES = "test_gpu_builder_matrix.py::test_size_ladder"
+TIES = "test_gpu_builder_matrix.py::test_equal_keys_keep_their_input_order"
+HEIGHTS = "test_gpu_builder_matrix.py::test_height_boundaries"
+LAYOUT0 = "test_gpu_builder_matrix.py::test_node_layout_0"
+BAD_FACE = "test_gpu_builder_matrix.py::test_bad_face_beyond_the_grid_cap"
+REFIT_STRUCT = "test_gpu_builder_matrix.py::test_refit_structure"
+REFIT_HANDLES = "test_gpu_builder_matrix.py::test_refit_of_loaded_saved_and_layout_0_handles"
 
 STATS_ONLY = ("instrumented launch (tr_trace_stats_query): its query results go to internal scratch that is freed "
               "unread, only the traversal counters come back -- there is nothing to compare with the oracle")
@@ -92,11 +100,14 @@ INVENTORY.update({
     "void k_closest_expand_slots_tiled<true, false>": (SLOTS,),
     "void k_closest_expand_slots_tiled<true, true>": (SLOTS,),
     # the builder: its output is a hierarchy, checked structurally and by a host traversal against the oracle
-    "k_tri_bounds": (BUILDER,), "k_init_bounds": (BUILDER,), "k_morton": (BUILDER,), "k_rs_count": (BUILDER,),
-    "k_rs_scan": (BUILDER,), "k_rs_scatter": (BUILDER,), "void k_karras<0>": (BUILDER,), "void k_karras<1>": (BUILDER,),
-    "k_refit_round": (BUILDER, REFIT), "k_emit": (BUILDER,), "k_gather": (BUILDER,), "k_regather": (BUILDER, UPDATE),
-    "k_layout_init": (BUILDER,), "k_layout_round": (BUILDER,), "k_qframe": (BUILDER,), "k_qframe_box": (BUILDER,),
-    "k_refit_nodes_round": (REFIT,), "k_update_boxes": (REFIT,),
+    "k_tri_bounds": (BUILDER, SIZES, BAD_FACE), "k_init_bounds": (BUILDER, SIZES), "k_morton": (BUILDER, SIZES),
+    "k_rs_count": (BUILDER, SIZES, TIES), "k_rs_scan": (BUILDER, SIZES, TIES), "k_rs_scatter": (BUILDER, SIZES, TIES),
+    "void k_karras<0>": (BUILDER, SIZES, HEIGHTS), "void k_karras<1>": (BUILDER, HEIGHTS),    # (launched only when plain keys give a height above 64)
+    "k_refit_round": (BUILDER, REFIT, SIZES, HEIGHTS), "k_emit": (BUILDER, SIZES, HEIGHTS, LAYOUT0), "k_gather": (BUILDER, SIZES),
+    "k_regather": (BUILDER, UPDATE, REFIT_STRUCT, REFIT_HANDLES, BAD_FACE),
+    "k_layout_init": (BUILDER, SIZES), "k_layout_round": (BUILDER, SIZES, HEIGHTS), "k_qframe": (BUILDER, SIZES),
+    "k_qframe_box": (REFIT, REFIT_STRUCT, REFIT_HANDLES),
+    "k_refit_nodes_round": (REFIT, REFIT_STRUCT, REFIT_HANDLES), "k_update_boxes": (REFIT, REFIT_STRUCT, REFIT_HANDLES),
     # the 8-wide nodes are built on first use by the launches that walk them
     "k_wide_mark": (WIDE, MATRIX), "k_wide_emit": (WIDE, MATRIX),
     "k_replica_hash": (REPLICA,),
