@@ -172,7 +172,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
         const unsigned long long idle = __ballot(done);
         if (idle == ~0ull) break;
         if (__popcll(idle) >= TR_STEAL_IDLE) {
-            const W cand = fs.trail & fs.owned;      // owed far children that are still in the ring
+            const W cand = fs.trail & fs.owned;      // owed far children that are in the stack
             const bool can_give = !done && cand != 0 && trip >= steal_min;
             const unsigned long long donors = __ballot(can_give);
             const int ni = __popcll(idle), nd = __popcll(donors);
@@ -188,12 +188,12 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                 const bool give = can_give && drank < np;
                 int gnode = 0, gdepth = 0;
                 if (give) {
-                    const uint32_t j = (uint32_t)__builtin_ctzll((unsigned long long)cand);
-                    gnode = tr_ring_get(ring, j & (TR_RING - 1));
+                    // the shallowest = the bottom of the stack; its owned bit stays behind and keeps the others' slots (tr_ring)
+                    uint32_t j;
+                    gnode = tr_ring_get(ring, tr_bottom_slot<W>(fs.trail, fs.owned, j));
                     gdepth = (int32_t)(j + 1);
                     list[drank] = lane; xnode[lane] = gnode; xdepth[lane] = gdepth;
                     fs.trail &= ~(W(1) << j);
-                    fs.owned &= ~(W(1) << j);
                 }
                 __builtin_amdgcn_wave_barrier();
                 const bool take = done && irank < np;
@@ -387,7 +387,7 @@ __device__ __forceinline__ int wave_count_unordered_steal(const tr_bvh_view& b, 
         const unsigned long long idle = __ballot(done);
         if (idle == ~0ull) break;
         if (idle == 0ull) continue;
-        const W cand = st.trail & st.owned;          // owed far children that are still in the ring
+        const W cand = st.trail & st.owned;          // owed far children that are in the stack
         const bool can_give = !done && cand != 0 && trip >= steal_min;
         const unsigned long long donors = __ballot(can_give);
         const int ni = __popcll(idle), nd = __popcll(donors);
@@ -408,7 +408,7 @@ __device__ __forceinline__ int wave_count_unordered_steal(const tr_bvh_view& b, 
         int gnode = 0, gdepth = 0;
         if (give) {
             const uint32_t j = (uint32_t)__builtin_ctzll((unsigned long long)cand);     // the shallowest: the biggest subtree
-            gnode = tr_ring_get(ring, j & (TR_RING - 1));
+            gnode = tr_ring_get(ring, j & (TR_RING - 1));      // (this schedule's ring is indexed by depth: tr_unord_step)
             gdepth = (int)(j + 1);
             st.trail &= ~(W(1) << j);
             st.owned &= ~(W(1) << j);

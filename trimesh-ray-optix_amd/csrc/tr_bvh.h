@@ -436,15 +436,24 @@ TR_HD bool tr_drain_exact(const tr_bvh_view& b, const tr_ray& r, int32_t& pe, tr
     return fin;
 }
 
-// Far-child ring: the far child pushed at depth k is remembered in slot k % TR_RING of a
-// per-lane ring (LDS on the GPU: slot s of lane t lives at base[s * stride], stride = block
-// size, so a wave's accesses are bank-conflict free whatever the per-lane depths are).  A
-// 64-bit `owned` mask says which depths still own their slot; backtracking reads the slot
-// (one LDS read) when owned and falls back to climbing the parent links otherwise.
+// Far-child stack: TR_RING words per lane (LDS on the GPU: word s of lane t lives at base[s * stride], stride =
+// block size, so a wave's accesses are bank-conflict free whatever the per-lane depths are).  Far children are owed
+// at strictly increasing depths and paid deepest first, so the words are a DENSE stack indexed by RANK, not by
+// depth: the entry owed at depth j sits in slot popcount(owned & ((1 << j) - 1)) mod N, a push goes to slot
+// popcount(owned) mod N.  `owned` has a bit per depth whose far child went into the stack; a pop at depth j
+// clears every bit from j upwards, so after it popcount(owned) IS the popped entry's slot.  The stealing hand-over
+// (kernels_direct.inc) takes the SHALLOWEST entry -- the bottom of the stack -- by clearing its trail bit only:
+// the owned bit stays behind as a ghost below every live entry, which keeps the ranks (and so the slots) of the
+// others; that is why slots wrap mod N, and why the live entries are trail & owned.  A hierarchy can be 64 levels
+// deep but a ray owes few far children AT ONCE (headline: 13 at most): a push that finds all N = TR_RING slots taken
+// by live entries is not recorded (no owned bit) and that far child -- the deepest one owed, the next to be paid, the
+// shortest way up -- is found by climbing the parent links, as without a stack.
+// (Tried and measured slower: 8 slots of {node, entry distance} with entries beyond the cull limit dropped at the pop:
+// DESIGN_experiments.md part R7.)
+// The unordered schedule (tr_unord_step) keeps the same words as a ring of 16 nodes indexed by depth % 16.
 #define TR_RING 16
-#define TR_RING_MASK 0x0001000100010001ull
 struct tr_ring {
-    int32_t* base;   // nullptr = no ring (always climb)
+    int32_t* base;   // nullptr = no stack (always climb)
     int32_t stride;
 };
 // Ring accesses go through an explicit LDS pointer on the device.  With the generic pointer the compiler
@@ -476,7 +485,7 @@ struct tr_state_t {
     int32_t node;     // next internal node to visit, -1 = hierarchy exhausted
     uint32_t depth;
     W trail;          // bit k: the node at depth k on the current path still owes its far child
-    W owned;          // bit k: that far child is still in ring slot k % TR_RING
+    W owned;          // bit k: that far child went into the far-child stack; its slot is its rank among the set bits (tr_ring)
     // leaves found by earlier node visits (tri slots, -1 = none), tested one per trip so that their triangle loads
     // overlap the next node's load (one memory round trip per iteration); up to two arrive per visit
     int32_t p0, p1, p2;
@@ -487,8 +496,39 @@ typedef tr_state_t<uint32_t> tr_state32;
 
 TR_HD uint32_t tr_top_bit(uint64_t x) { return 63u - (uint32_t)__builtin_clzll(x); }
 TR_HD uint32_t tr_top_bit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
-TR_HD uint64_t tr_ring_mask(uint64_t) { return TR_RING_MASK; }
+TR_HD uint64_t tr_ring_mask(uint64_t) { return 0x0001000100010001ull; }      // the depths that share a slot of the unordered schedule's ring (tr_unord_step)
 TR_HD uint32_t tr_ring_mask(uint32_t) { return 0x00010001u; }
+TR_HD uint32_t tr_popc(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }
+TR_HD uint32_t tr_popc(uint32_t x) { return (uint32_t)__builtin_popcount(x); }
+
+// Far-child stack (tr_ring): push the far child owed at `depth` (every trail / owned bit is below `depth`).
+template <typename W>
+TR_HD void tr_push_far(const tr_ring ring, W trail, W& owned, uint32_t depth, int32_t node) {
+    if (ring.base && tr_popc(owned & trail) < TR_RING) {      // (live entries: a hand-over leaves owned bits without a trail bit)
+        tr_ring_put(ring, tr_popc(owned) & (TR_RING - 1), node);
+        owned |= W(1) << depth;
+    }
+}
+// Pay the deepest far child still owed (trail != 0), the one at depth j.  Returns true: `node` comes from the stack;
+// false: it is not in the stack (a push onto a full one, or no stack at all) and the caller climbs to it.
+template <typename W>
+TR_HD bool tr_pop_far(const tr_ring ring, W& trail, W& owned, uint32_t& j, int32_t& node) {
+    j = tr_top_bit(trail);
+    const W bit = W(1) << j;
+    trail &= ~bit;
+    const bool own = (owned & bit) != 0;
+    owned &= bit - 1;                                   // this entry and what a hand-over left behind above it
+    if (!(ring.base && own)) return false;
+    node = tr_ring_get(ring, tr_popc(owned) & (TR_RING - 1));
+    return true;
+}
+// the slot of the SHALLOWEST live entry (trail & owned != 0), which the stealing launches hand to an idle lane; the
+// caller clears its trail bit and leaves the owned bit where it is (tr_ring)
+template <typename W>
+TR_HD uint32_t tr_bottom_slot(W trail, W owned, uint32_t& j) {
+    j = (uint32_t)__builtin_ctzll((unsigned long long)(trail & owned));
+    return tr_popc((W)(owned & ((W(1) << j) - 1))) & (TR_RING - 1);
+}
 
 template <typename W>
 TR_HD void tr_state_init(tr_state_t<W>& st) {
@@ -553,12 +593,8 @@ TR_HD void tr_node_step(const tr_bvh_view& b, const tr_ray& r, tr_state& st, con
         const bool both = h0 & h1;
         const bool swap = both ? (tn1 < tn0) : h1;   // descend into c1?
         if (both) {
+            tr_push_far(ring, st.trail, st.owned, st.depth, swap ? c0 : c1);
             st.trail |= (1ull << st.depth);
-            if (ring.base) {
-                const uint32_t slot = st.depth & (TR_RING - 1);
-                tr_ring_put(ring, slot, swap ? c0 : c1);
-                st.owned = (st.owned & ~(TR_RING_MASK << slot)) | (1ull << st.depth);
-            }
         }
         st.node = swap ? c1 : c0;
         st.depth++;
@@ -566,10 +602,10 @@ TR_HD void tr_node_step(const tr_bvh_view& b, const tr_ray& r, tr_state& st, con
         st.node = -1;
     } else {
         // backtrack to the deepest ancestor that still owes its far child
-        const uint32_t j = 63u - (uint32_t)__builtin_clzll(st.trail);
-        st.trail &= ~(1ull << j);
-        if (ring.base && ((st.owned >> j) & 1ull)) {
-            st.node = tr_ring_get(ring, j & (TR_RING - 1));
+        uint32_t j = 0;
+        int32_t far = -1;
+        if (tr_pop_far(ring, st.trail, st.owned, j, far)) {
+            st.node = far;
         } else {
             int32_t node = st.node;
             uint32_t depth = st.depth;
@@ -788,36 +824,33 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
             const bool both = h0 && h1;
             const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
             if (both) {
+                tr_push_far(ring, st.trail, st.owned, st.depth, swap ? c0 : c1);
                 st.trail |= (W(1) << st.depth);
-                if (ring.base) {
-                    const uint32_t slot = st.depth & (TR_RING - 1);
-                    tr_ring_put(ring, slot, swap ? c0 : c1);
-                    st.owned = (st.owned & ~(tr_ring_mask(W(0)) << slot)) | (W(1) << st.depth);
-                }
             }
             st.node = swap ? c1 : c0;
             st.depth++;
         } else if (st.trail == 0) {
             st.node = -1;
         } else {
-            const uint32_t j = tr_top_bit(st.trail);
-            st.trail &= ~(W(1) << j);
-            if (ring.base && ((st.owned >> j) & W(1))) {
-                st.node = tr_ring_get(ring, j & (TR_RING - 1));
-            } else if constexpr (std::is_same<REC, tr_rec_f>::value) {
-                int32_t node = st.node;
-                uint32_t depth = st.depth;
-                while (depth > j + 1) {
-                    node = parent;
-                    const tr_link l = b.links[node];
-                    parent = l.parent; sibling = l.sibling;
-                    depth--;
-                    if (STATS) cnt->climbs++;
+            uint32_t j = 0;
+            int32_t far = -1;
+            if (!tr_pop_far(ring, st.trail, st.owned, j, far)) {      // not in the stack (the rare push onto a full one): climb
+                if constexpr (std::is_same<REC, tr_rec_f>::value) {
+                    int32_t node = st.node;
+                    uint32_t depth = st.depth;
+                    while (depth > j + 1) {
+                        node = parent;
+                        const tr_link l = b.links[node];
+                        parent = l.parent; sibling = l.sibling;
+                        depth--;
+                        if (STATS) cnt->climbs++;
+                    }
+                    far = sibling;
+                } else {
+                    far = tr_climb<STATS>(b, st.node, st.depth, j, cnt);
                 }
-                st.node = sibling;
-            } else {
-                st.node = tr_climb<STATS>(b, st.node, st.depth, j, cnt);
             }
+            st.node = far;
             st.depth = j + 1;
         }
     }
@@ -967,6 +1000,10 @@ TR_HD void tr_unord_step(const tr_bvh_view& b, const tr_ray& r, bool go_node, bo
         if (h0 || h1) {
             const bool both = h0 && h1;
             const bool swap = (Q == TR_Q_ANY) ? ((both && tn1 < tn0) || !h0) : !h0;   // descend into c1?
+            // (this schedule keeps the words as a RING of 16 nodes indexed by depth: slot = depth % 16, a push takes the
+            // slot from the entry 16 levels up, which is then found by climbing.  The dense stack of the fused trip costs
+            // these kernels two registers -- the 64-bit-addressing count launch a wave per SIMD -- and they have no cull
+            // limit to drop entries by.)
             if (both) {
                 st.trail |= (W(1) << st.depth);
                 if (ring.base) {
