@@ -46,10 +46,16 @@ static void *to_device(const void *h, size_t bytes) {
     if (bytes) CHECK_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
     return d;
 }
+/* Every output is refilled before the call that writes it, with a pattern the expectations that follow reject: 0xa5 in
+ * every byte for the byte and integer arrays (a hit / front byte is 0 or 1; an index, a slot or a count is >= -1, and bit 31
+ * of a record's first word says "miss"), 0xff for the float arrays (a NaN: feq() and == fail on it; 0xa5a5a5a5 would read
+ * as -2.87e-16 and pass feq(x, 0.f)). */
+static void poison(void *d, size_t bytes) { CHECK_HIP(hipMemset(d, 0xa5, bytes ? bytes : 4)); }
+static void poison_f(float *d, size_t bytes) { CHECK_HIP(hipMemset(d, 0xff, bytes ? bytes : 4)); }
 static void *device_zeros(size_t bytes) {
     void *d = NULL;
     CHECK_HIP(hipMalloc(&d, bytes ? bytes : 4));
-    CHECK_HIP(hipMemset(d, 0xcd, bytes ? bytes : 4)); /* outputs must be fully written by the library */
+    poison(d, bytes); /* outputs must be fully written by the library */
     return d;
 }
 static void to_host(void *h, const void *d, size_t bytes) { CHECK_HIP(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); }
@@ -107,6 +113,7 @@ int main(void) {
     d_hit = (uint8_t *)device_zeros(2); d_front = (uint8_t *)device_zeros(2);
     d_tri = (int32_t *)device_zeros(8); d_cnt = (int32_t *)device_zeros(8);
     d_loc = (float *)device_zeros(24); d_uv = (float *)device_zeros(16);
+    poison_f(d_loc, 24); poison_f(d_uv, 16);
 
     CHECK_TR(tr_intersects_any(bvh, &rays, d_hit, NULL));
     to_host(hit, d_hit, 2);
@@ -114,6 +121,7 @@ int main(void) {
     CHECK_TR(tr_intersects_first(bvh, &rays, d_tri, NULL));
     to_host(tri, d_tri, 8);
     EXPECT(tri[0] == 1 && tri[1] == 0);
+    poison(d_hit, 2); poison(d_tri, 8);      /* (written by the two calls above: every call meets poisoned outputs) */
     CHECK_TR(tr_intersects_closest(bvh, &rays, d_hit, d_front, d_tri, d_loc, d_uv, NULL));
     to_host(hit, d_hit, 2); to_host(front, d_front, 2); to_host(tri, d_tri, 8); to_host(loc, d_loc, 24); to_host(uv, d_uv, 16);
     EXPECT(hit[0] == 1 && front[0] == 0 && tri[0] == 1);      /* from below: back face of the lower triangle */
@@ -128,7 +136,7 @@ int main(void) {
     d_off = (int64_t *)device_zeros(16); d_total = (int64_t *)device_zeros(8);
     CHECK_TR(tr_hits_scan(d_cnt, 2, TR_MAX_ANYHIT_SIZE, d_off, d_total, &total, NULL));
     EXPECT(total == 4);
-    d_hloc = (float *)device_zeros(48); d_hray = (int32_t *)device_zeros(16); d_htri = (int32_t *)device_zeros(16);
+    d_hloc = (float *)device_zeros(48); poison_f(d_hloc, 48); d_hray = (int32_t *)device_zeros(16); d_htri = (int32_t *)device_zeros(16);
     CHECK_TR(tr_intersects_location_fill(bvh, &rays, TR_MAX_ANYHIT_SIZE, d_off, d_hloc, d_hray, d_htri, 0, NULL));
     to_host(hloc, d_hloc, 48); to_host(hray, d_hray, 16); to_host(htri, d_htri, 16);
     EXPECT(hray[0] == 0 && hray[1] == 0 && hray[2] == 1 && hray[3] == 1);
@@ -142,7 +150,8 @@ int main(void) {
         int32_t *d_f2 = (int32_t *)to_device(faces, sizeof faces);
         int form;
         for (form = 0; form < 3; form++) {
-            CHECK_HIP(hipMemset(d_hit, 7, 2)); CHECK_HIP(hipMemset(d_loc, 0xff, 24));
+            poison(d_rec, 2 * sizeof(tr_packed_hit));
+            poison(d_hit, 2); poison(d_front, 2); poison(d_tri, 8); poison_f(d_loc, 24); poison_f(d_uv, 16);
             if (form == 0) {
                 CHECK_TR(tr_intersects_closest_packed(bvh, &rays, d_rec, NULL));
                 CHECK_TR(tr_closest_expand(d_rec, 2, d_v2, 6, d_f2, 2, d_hit, d_front, d_tri, d_loc, d_uv, NULL));
@@ -162,7 +171,7 @@ int main(void) {
     /* ... and as 4-byte records for a destination that holds the rays (ABI 8): the slot, then the end of the query */
     {
         int32_t *d_slot = (int32_t *)device_zeros(8), slot[2];
-        CHECK_HIP(hipMemset(d_hit, 7, 2)); CHECK_HIP(hipMemset(d_loc, 0xff, 24));
+        poison(d_hit, 2); poison(d_front, 2); poison(d_tri, 8); poison_f(d_loc, 24); poison_f(d_uv, 16);
         CHECK_TR(tr_intersects_closest_slots(bvh, &rays, d_slot, NULL));
         to_host(slot, d_slot, 8);
         EXPECT(slot[0] >= 0 && slot[0] < 2 && slot[1] >= 0 && slot[1] < 2 && slot[0] != slot[1]);
@@ -185,11 +194,13 @@ int main(void) {
         CHECK_HIP(hipMemcpy(d_o, o1, sizeof o1, hipMemcpyHostToDevice));
         CHECK_HIP(hipMemcpy(d_d, dd1, sizeof dd1, hipMemcpyHostToDevice));
         CHECK_TR(tr_bvh_update(bvh, d_v, 3, d_f, 1, NULL));
+        poison(d_hit, 2); poison(d_front, 2); poison(d_tri, 8); poison_f(d_loc, 24); poison_f(d_uv, 16);
         CHECK_TR(tr_intersects_closest(bvh, &rays, d_hit, d_front, d_tri, d_loc, d_uv, NULL));
         to_host(hit, d_hit, 2); to_host(front, d_front, 2); to_host(tri, d_tri, 8); to_host(loc, d_loc, 24); to_host(uv, d_uv, 16);
         EXPECT(hit[0] == 1 && front[0] == 1 && tri[0] == 0 && feq(loc[2], 0.f) && feq(uv[0], 0.25f) && feq(uv[1], 0.5f));
         EXPECT(hit[1] == 0 && front[1] == 0 && tri[1] == -1 && loc[3] == 0.f && loc[4] == 0.f && loc[5] == 0.f && uv[2] == 0.f && uv[3] == 0.f);
         rays = flat_rays(d_o, d_d, 2, 0);           /* origin (0,0,4) for both rays: stride 0 (README.md:35-39) */
+        poison(d_hit, 2);
         CHECK_TR(tr_intersects_any(bvh, &rays, d_hit, NULL));
         to_host(hit, d_hit, 2);
         EXPECT(hit[0] == 1 && hit[1] == 0);         /* (0,0,4) + t (0,1,0) passes above the triangle */

@@ -19,6 +19,9 @@ import workloads as W  # noqa: E402
 import triro.backend.ops as hops  # noqa: E402
 from triro.ray.ray_optix import RayMeshIntersector  # noqa: E402
 from triro.ray.sharded import EmulatedWorld, ShardedRayMeshIntersector, dst_bounds, shard_bounds  # noqa: E402
+import poison  # noqa: E402
+
+poison.install()      # every output and gather buffer is born poisoned, every eager ops result is checked for unwritten elements
 
 dev = torch.device("cuda:0")
 torch.cuda.set_device(dev)

@@ -15,6 +15,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "trimesh-ray-optix_amd")]
 import workloads as W  # noqa: E402
 from triro.ray.ray_optix import RayMeshIntersector  # noqa: E402
 from triro.ray.sharded import ShardedRayMeshIntersector  # noqa: E402
+import poison  # noqa: E402
+
+poison.install()      # every output and gather buffer is born poisoned, every eager ops result is checked for unwritten elements
 
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
 os.environ.setdefault("MASTER_PORT", sys.argv[1] if len(sys.argv) > 1 else "29611")

@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c_client", "client.c")
 OUT = os.path.join(ROOT, "tests", "c_client", "_build", "client")

@@ -10,6 +10,7 @@ import pytest
 import workloads as W
 from geom64 import closest_f64
 from oracle.oracle import OracleIntersector
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 CASES = {
     "icosphere3_hash": lambda: (W.icosphere(3), W.hash_rays(6000, 11, [-1.6] * 3, [1.6] * 3)),

@@ -33,6 +33,7 @@ from launch_options import options
 from oracle.oracle import OracleIntersector
 from sim import SimBVH
 from test_builder_reference import copies_of_one_triangle, named_mesh, same_tree_under_a_permutation
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 

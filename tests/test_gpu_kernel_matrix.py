@@ -23,6 +23,7 @@ import torch
 import workloads as W
 from launch_options import options
 from oracle.oracle import OracleIntersector
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 

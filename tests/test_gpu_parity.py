@@ -11,6 +11,7 @@ import torch
 
 import workloads as W
 from oracle.oracle import OracleIntersector
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")

@@ -18,6 +18,8 @@ import torch
 import workloads as W
 from launch_options import options, restore_defaults
 from oracle.oracle import OracleIntersector
+import poison
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 
@@ -432,6 +434,7 @@ def test_queries_can_be_captured_in_a_hip_graph(device):
         ot.copy_(T(o, device) + 0.01 * k)        # new rays in the captured input buffers
         g.replay()
         torch.cuda.synchronize()
+        poison.assert_written(*out, cnt, what=f"graph replay {k}")      # (the captured fill re-poisons before every replay)
         exp = R.closest_raw((o + np.float32(0.01 * k)).astype(np.float32), d)
         assert_closest_bitexact(out, exp, f"graph replay {k}")
         assert np.array_equal(cnt.cpu().numpy(), R.intersects_count((o + np.float32(0.01 * k)).astype(np.float32), d))
@@ -455,6 +458,7 @@ def test_queries_can_be_captured_in_a_hip_graph(device):
         assert np.array_equal(c2.cpu().numpy(), cnt2)
         g.replay()
         torch.cuda.synchronize()
+        poison.assert_written(*out, cnt, what=f"graph replay after another batch size {k}")
         assert_closest_bitexact(out, exp, f"graph replay after another batch size {k}")
         assert np.array_equal(cnt.cpu().numpy(), R.intersects_count(o, d))
 

@@ -6,6 +6,8 @@ import torch
 import workloads as W
 from oracle.oracle import OracleIntersector
 from test_gpu_round2 import T, make, assert_closest_bitexact, on_surface_rays
+import poison
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +186,7 @@ def test_a_graph_recorded_while_a_sort_is_pending(device):
     for k in range(3):
         g.replay()
         torch.cuda.synchronize()
+        poison.assert_written(*out, what=f"replay {k}")
         assert_closest_bitexact(out, exp, f"replay {k}")
     with torch.cuda.stream(side):
         got = r.intersects_closest(O, D)         # the next real launch on the stream carries the pending sort
@@ -195,4 +198,5 @@ def test_a_graph_recorded_while_a_sort_is_pending(device):
     assert_closest_bitexact(got, exp, "eager launches after the recording")
     g.replay()
     torch.cuda.synchronize()
+    poison.assert_written(*out, what="replay after more eager launches")
     assert_closest_bitexact(out, exp, "replay after more eager launches")

@@ -7,6 +7,8 @@ import torch
 import workloads as W
 from oracle.oracle import OracleIntersector
 from test_gpu_round2 import T, make
+import poison
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 
@@ -209,6 +211,7 @@ def test_graph_replay_follows_a_refit_that_moves_the_bounds(device):
         r.refit(T(vv, device))
         graph.replay()
         torch.cuda.synchronize()
+        poison.assert_written(*out, cnt, what="graph replay after a refit")
         R = OracleIntersector(vv, f, mode=1)
         eh, ef, et, el, eu = R.intersects_closest(o, d)
         assert np.array_equal(out[0].cpu().numpy(), eh) and np.array_equal(out[2].cpu().numpy(), et)

@@ -8,6 +8,7 @@ import torch
 
 import workloads as W
 from oracle.oracle import OracleIntersector
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 EYE, TARGET = (-2.2, 0.6, -1.8), (0.2, -0.1, 0.1)

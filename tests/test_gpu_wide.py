@@ -6,6 +6,8 @@ import torch
 
 import workloads as W
 from oracle.oracle import OracleIntersector
+import poison
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
 
 pytestmark = pytest.mark.gpu
 
@@ -174,6 +176,7 @@ def test_graph_replay_of_a_wide_launch_follows_a_refit(device, opts):
         out = r.intersects_closest(o, d)
     graph.replay()
     torch.cuda.synchronize()
+    poison.assert_written(*out, what="graph replay on the wide nodes")
     R = OracleIntersector(v, f, mode=1)
     e = R.intersects_closest(o.cpu().numpy(), d.cpu().numpy())
     assert np.array_equal(out[2].cpu().numpy(), e[2]) and np.array_equal(out[3].cpu().numpy(), e[3])
@@ -181,6 +184,7 @@ def test_graph_replay_of_a_wide_launch_follows_a_refit(device, opts):
     r.refit(torch.from_numpy(v2).to(device))
     graph.replay()
     torch.cuda.synchronize()
+    poison.assert_written(*out, what="graph replay on the wide nodes after a refit")
     e2 = OracleIntersector(v2, f, mode=1).intersects_closest(o.cpu().numpy(), d.cpu().numpy())
     assert not np.array_equal(e2[2], e[2])
     assert np.array_equal(out[0].cpu().numpy(), e2[0]) and np.array_equal(out[2].cpu().numpy(), e2[2])

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from poison import poisoned_outputs  # noqa: F401  (autouse: every output is born poisoned, every eager result checked)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 

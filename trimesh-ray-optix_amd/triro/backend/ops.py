@@ -12,7 +12,7 @@ Differences that are deliberate: inputs are validated and err
 (ValueError / RuntimeError) instead of printing and returning undefined tensors
 (ray.cpp:104-123,164-165); float32 is enforced (the reference silently reinterprets other
 dtypes); work is enqueued on torch's CURRENT stream of the tensors' device instead of a
-private stream (base.cpp:34); outputs are allocated here with torch.empty and handed to the
+private stream (base.cpp:34); outputs are allocated here (_new_output: torch.empty) and handed to the
 library as raw pointers.
 
 There is no CPU fallback: without the library or without a GPU every query raises.
@@ -229,11 +229,17 @@ def _handle(accel_structure, rays_tensor=None):
     return h
 
 
+def _new_output(shape, dtype, device) -> torch.Tensor:
+    """Every tensor the library writes into -- results and the intermediates count / slots / offsets / total_d -- is born
+    here, uninitialised.  One seam, so that a run can swap it to see which bytes no kernel ever wrote (tests/poison.py)."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
 # --- queries (ops.py:84-192) ----------------------------------------------------------------------
 def intersects_any(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:84-100 / ray.cpp:161-189.  Bool[*b]."""
     check_rays(origins, dirs)
-    out = torch.empty(origins.shape[:-1], dtype=torch.bool, device=origins.device)
+    out = _new_output(origins.shape[:-1], torch.bool, origins.device)
     with torch.cuda.device(origins.device):
         _check(get_module().tr_intersects_any(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
                                               out.data_ptr(), _stream_ptr(origins.device)))
@@ -243,7 +249,7 @@ def intersects_any(accel_structure, origins, dirs) -> torch.Tensor:
 def intersects_first(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:103-119 / ray.cpp:191-219.  Int32[*b], -1 on miss."""
     check_rays(origins, dirs)
-    out = torch.empty(origins.shape[:-1], dtype=torch.int32, device=origins.device)
+    out = _new_output(origins.shape[:-1], torch.int32, origins.device)
     with torch.cuda.device(origins.device):
         _check(get_module().tr_intersects_first(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
                                                 out.data_ptr(), _stream_ptr(origins.device)))
@@ -264,11 +270,11 @@ def intersects_closest(accel_structure, origins, dirs, outs=None) -> Tuple[torch
             raise ValueError("outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on the rays' device")
         hit, front, tri, loc, uv = outs
     else:
-        hit = torch.empty(b, dtype=torch.bool, device=dev)
-        front = torch.empty(b, dtype=torch.bool, device=dev)
-        tri = torch.empty(b, dtype=torch.int32, device=dev)
-        loc = torch.empty((*b, 3), dtype=torch.float32, device=dev)
-        uv = torch.empty((*b, 2), dtype=torch.float32, device=dev)
+        hit = _new_output(b, torch.bool, dev)
+        front = _new_output(b, torch.bool, dev)
+        tri = _new_output(b, torch.int32, dev)
+        loc = _new_output((*b, 3), torch.float32, dev)
+        uv = _new_output((*b, 2), torch.float32, dev)
     with torch.cuda.device(dev):
         _check(get_module().tr_intersects_closest(
             _handle(accel_structure, origins), C.byref(make_rays(origins, dirs)), hit.data_ptr(), front.data_ptr(),
@@ -284,7 +290,7 @@ def intersects_closest_packed(accel_structure, origins, dirs, out: torch.Tensor 
     check_rays(origins, dirs)
     n, dev = origins.numel() // 3, origins.device
     if out is None:
-        out = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        out = _new_output((n, 3), torch.int32, dev)
     elif out.dtype != torch.int32 or tuple(out.shape) != (n, 3) or not out.is_contiguous() or out.device != dev:
         raise ValueError("out must be a contiguous int32 [n, 3] tensor on the rays' device")
     # slots: the record names the ARENA SLOT of the triangle instead of its face index (tr_intersects_closest_packed_slots):
@@ -302,7 +308,7 @@ def intersects_closest_slots(accel_structure, origins, dirs, out: torch.Tensor =
     check_rays(origins, dirs)
     n, dev = origins.numel() // 3, origins.device
     if out is None:
-        out = torch.empty((n,), dtype=torch.int32, device=dev)
+        out = _new_output((n,), torch.int32, dev)
     elif out.dtype != torch.int32 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != dev:
         raise ValueError("out must be a contiguous int32 [n] tensor on the rays' device")
     with torch.cuda.device(dev):
@@ -328,11 +334,11 @@ def closest_from_slots(accel_structure, origins, dirs, slots: torch.Tensor, outs
         hit, front, tri, loc, uv = outs
     else:
         b = origins.shape[:-1]
-        hit = torch.empty(b, dtype=torch.bool, device=dev)
-        front = torch.empty(b, dtype=torch.bool, device=dev)
-        tri = torch.empty(b, dtype=torch.int32, device=dev)
-        loc = torch.empty((*b, 3), dtype=torch.float32, device=dev)
-        uv = torch.empty((*b, 2), dtype=torch.float32, device=dev)
+        hit = _new_output(b, torch.bool, dev)
+        front = _new_output(b, torch.bool, dev)
+        tri = _new_output(b, torch.int32, dev)
+        loc = _new_output((*b, 3), torch.float32, dev)
+        uv = _new_output((*b, 2), torch.float32, dev)
     with torch.cuda.device(dev):
         _check(get_module().tr_closest_from_slots(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
                                                   slots.data_ptr(), int(row_length), hit.data_ptr(), front.data_ptr(),
@@ -354,11 +360,11 @@ def closest_expand_slots(accel_structure, packed: torch.Tensor, batch_shape=None
         hit, front, tri, loc, uv = outs
     else:
         b = tuple(batch_shape) if batch_shape is not None else (n,)
-        hit = torch.empty(b, dtype=torch.bool, device=dev)
-        front = torch.empty(b, dtype=torch.bool, device=dev)
-        tri = torch.empty(b, dtype=torch.int32, device=dev)
-        loc = torch.empty((*b, 3), dtype=torch.float32, device=dev)
-        uv = torch.empty((*b, 2), dtype=torch.float32, device=dev)
+        hit = _new_output(b, torch.bool, dev)
+        front = _new_output(b, torch.bool, dev)
+        tri = _new_output(b, torch.int32, dev)
+        loc = _new_output((*b, 3), torch.float32, dev)
+        uv = _new_output((*b, 2), torch.float32, dev)
         if hit.numel() != n:
             raise ValueError(f"batch_shape {b} does not hold {n} rays")
     # row_length: the records are whole rows of an image of that width (tr_closest_expand_slots_rows: 8x8 tiles per wave)
@@ -393,11 +399,11 @@ def closest_expand(packed: torch.Tensor, vertices: torch.Tensor, faces: torch.Te
                                                   faces.data_ptr(), faces.shape[0], *(t.data_ptr() for t in outs), _stream_ptr(dev)))
         return tuple(outs)
     b = tuple(batch_shape) if batch_shape is not None else (n,)
-    hit = torch.empty(b, dtype=torch.bool, device=dev)
-    front = torch.empty(b, dtype=torch.bool, device=dev)
-    tri = torch.empty(b, dtype=torch.int32, device=dev)
-    loc = torch.empty((*b, 3), dtype=torch.float32, device=dev)
-    uv = torch.empty((*b, 2), dtype=torch.float32, device=dev)
+    hit = _new_output(b, torch.bool, dev)
+    front = _new_output(b, torch.bool, dev)
+    tri = _new_output(b, torch.int32, dev)
+    loc = _new_output((*b, 3), torch.float32, dev)
+    uv = _new_output((*b, 2), torch.float32, dev)
     if hit.numel() != n:
         raise ValueError(f"batch_shape {b} does not hold {n} rays")
     with torch.cuda.device(dev):
@@ -410,7 +416,7 @@ def closest_expand(packed: torch.Tensor, vertices: torch.Tensor, faces: torch.Te
 def intersects_count(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:152-168 / ray.cpp:291-322.  Int32[*b]."""
     check_rays(origins, dirs)
-    out = torch.empty(origins.shape[:-1], dtype=torch.int32, device=origins.device)
+    out = _new_output(origins.shape[:-1], torch.int32, origins.device)
     with torch.cuda.device(origins.device):
         _check(get_module().tr_intersects_count(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
                                                 out.data_ptr(), _stream_ptr(origins.device)))
@@ -434,19 +440,19 @@ def intersects_location(accel_structure, origins, dirs, ray_base: int = 0, fused
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
             rays = make_rays(origins, dirs)
-            count = torch.empty(n, dtype=torch.int32, device=dev)
-            slots = torch.empty((n, MAX_ANYHIT_SIZE, 2), dtype=torch.int32, device=dev)   # tr_hit_entry {t_key, slot}
+            count = _new_output(n, torch.int32, dev)
+            slots = _new_output((n, MAX_ANYHIT_SIZE, 2), torch.int32, dev)   # tr_hit_entry {t_key, slot}
             _check(lib.tr_intersects_count_topk(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
                                                 count.data_ptr(), slots.data_ptr(), stream))
-            offsets = torch.empty(n, dtype=torch.int64, device=dev)
-            total_d = torch.empty(1, dtype=torch.int64, device=dev)
+            offsets = _new_output(n, torch.int64, dev)
+            total_d = _new_output(1, torch.int64, dev)
             total = C.c_int64(0)
             _check(lib.tr_hits_scan(count.data_ptr(), n, MAX_ANYHIT_SIZE, offsets.data_ptr(), total_d.data_ptr(),
                                     C.byref(total), stream))
             nhits = int(total.value)
-            loc = torch.empty((nhits, 3), dtype=torch.float32, device=dev)
-            tri = torch.empty(nhits, dtype=torch.int32, device=dev)
-            ray = torch.empty(nhits, dtype=torch.int32, device=dev)
+            loc = _new_output((nhits, 3), torch.float32, dev)
+            tri = _new_output(nhits, torch.int32, dev)
+            ray = _new_output(nhits, torch.int32, dev)
             _check(lib.tr_location_fill_slots(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
                                               count.data_ptr(), offsets.data_ptr(), slots.data_ptr(),
                                               loc.data_ptr(), ray.data_ptr(), tri.data_ptr(), ray_base, stream))
@@ -454,17 +460,17 @@ def intersects_location(accel_structure, origins, dirs, ray_base: int = 0, fused
     with torch.cuda.device(dev):
         stream = _stream_ptr(dev)
         rays = make_rays(origins, dirs)
-        count = torch.empty(n, dtype=torch.int32, device=dev)
+        count = _new_output(n, torch.int32, dev)
         _check(lib.tr_intersects_count(_handle(accel_structure, origins), C.byref(rays), count.data_ptr(), stream))
-        offsets = torch.empty(n, dtype=torch.int64, device=dev)
-        total_d = torch.empty(1, dtype=torch.int64, device=dev)
+        offsets = _new_output(n, torch.int64, dev)
+        total_d = _new_output(1, torch.int64, dev)
         total = C.c_int64(0)
         _check(lib.tr_hits_scan(count.data_ptr(), n, MAX_ANYHIT_SIZE, offsets.data_ptr(), total_d.data_ptr(),
                                 C.byref(total), stream))   # host sync == ray.cpp:339 .item<int>()
         nhits = int(total.value)
-        loc = torch.empty((nhits, 3), dtype=torch.float32, device=dev)
-        tri = torch.empty(nhits, dtype=torch.int32, device=dev)
-        ray = torch.empty(nhits, dtype=torch.int32, device=dev)
+        loc = _new_output((nhits, 3), torch.float32, dev)
+        tri = _new_output(nhits, torch.int32, dev)
+        ray = _new_output(nhits, torch.int32, dev)
         _check(lib.tr_intersects_location_fill(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
                                                offsets.data_ptr(), loc.data_ptr(), ray.data_ptr(),
                                                tri.data_ptr(), ray_base, stream))
@@ -491,16 +497,16 @@ def compact_closest(hit, front, tri, loc, uv, ray_base: int = 0):
     _check_ray_idx_range(n, ray_base, "stream compaction")
     with torch.cuda.device(dev):
         stream = _stream_ptr(dev)
-        offsets = torch.empty(n, dtype=torch.int64, device=dev)
-        total_d = torch.empty(1, dtype=torch.int64, device=dev)
+        offsets = _new_output(n, torch.int64, dev)
+        total_d = _new_output(1, torch.int64, dev)
         total = C.c_int64(0)
         _check(lib.tr_mask_scan(hit.data_ptr(), n, offsets.data_ptr(), total_d.data_ptr(), C.byref(total), stream))
         h = int(total.value)
-        front_o = torch.empty(h, dtype=torch.bool, device=dev) if front is not None else None
-        ray_o = torch.empty(h, dtype=torch.int32, device=dev)
-        tri_o = torch.empty(h, dtype=torch.int32, device=dev) if tri is not None else None
-        loc_o = torch.empty((h, 3), dtype=torch.float32, device=dev) if loc is not None else None
-        uv_o = torch.empty((h, 2), dtype=torch.float32, device=dev) if uv is not None else None
+        front_o = _new_output(h, torch.bool, dev) if front is not None else None
+        ray_o = _new_output(h, torch.int32, dev)
+        tri_o = _new_output(h, torch.int32, dev) if tri is not None else None
+        loc_o = _new_output((h, 3), torch.float32, dev) if loc is not None else None
+        uv_o = _new_output((h, 2), torch.float32, dev) if uv is not None else None
         p = lambda t: t.data_ptr() if t is not None else None
         _check(lib.tr_compact_closest(hit.data_ptr(), offsets.data_ptr(), n, p(front), p(tri), p(loc), p(uv),
                                       ray_base, p(front_o), ray_o.data_ptr(), p(tri_o), p(loc_o), p(uv_o), stream))

@@ -64,6 +64,12 @@ import torch
 import torch.distributed as dist
 
 
+def _new_output(shape, dtype, device):
+    """Every tensor this module only writes into -- results, gather and staging buffers -- is born here (as in
+    triro.backend.ops): the one place to swap when a run wants to see which bytes nothing ever wrote."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
 def shard_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
     """Contiguous chunk [lo, hi) of rank `rank`; chunks differ by at most one ray."""
     base, rem = divmod(n, world)
@@ -454,7 +460,7 @@ class ShardedRayMeshIntersector:
             else:
                 cdev = torch.device("cpu") if self._stage or not torch.cuda.is_available() else torch.device("cuda", torch.cuda.current_device())
                 mine = torch.tensor([fp, rec], dtype=torch.int64, device=cdev)
-                every = torch.empty((2 * self.world,), dtype=torch.int64, device=cdev)
+                every = _new_output((2 * self.world,), torch.int64, cdev)
                 dist.all_gather_into_tensor(every, mine, group=self._xg)
                 got = [int(x) for x in every.tolist()]
             vals, recs = got[0::2], got[1::2]
@@ -523,7 +529,7 @@ class ShardedRayMeshIntersector:
     # 2.6 GB.  Every allocation of this module goes through _alloc (tests count them).
     @staticmethod
     def _alloc(shape, dtype, device):
-        return torch.empty(shape, dtype=dtype, device=device)
+        return _new_output(shape, dtype, device)
 
     def _staged(self, t: torch.Tensor) -> bool:
         return self._stage and (t.is_cuda or self._stage_cpu_too)
@@ -557,7 +563,7 @@ class ShardedRayMeshIntersector:
             src_x = src.detach().cpu()
             views = None
             if want:
-                views = [src_x if r == rank else torch.empty((sizes[r], *src.shape[1:]), dtype=src.dtype) for r in range(world)]
+                views = [src_x if r == rank else _new_output((sizes[r], *src.shape[1:]), src.dtype, src_x.device) for r in range(world)]
                 copies = [(out[bounds[r][0]:bounds[r][1]], views[r]) for r in range(world) if r != rank and sizes[r] > 0]
         else:
             src_x = src
@@ -573,11 +579,11 @@ class ShardedRayMeshIntersector:
                     w = dist.all_gather_into_tensor(out, src_x, group=self._xg, async_op=async_op)
                 else:       # chunk k of every rank: the slices are not adjacent in `out`
                     if staged:
-                        views = [torch.empty_like(src_x) if r == rank else v for r, v in enumerate(views)]
+                        views = [_new_output(src_x.shape, src_x.dtype, src_x.device) if r == rank else v for r, v in enumerate(views)]
                     w = dist.all_gather(views, src_x, group=self._xg, async_op=async_op)
             else:
                 if staged and want:
-                    views = [torch.empty_like(src_x) if r == rank else v for r, v in enumerate(views)]
+                    views = [_new_output(src_x.shape, src_x.dtype, src_x.device) if r == rank else v for r, v in enumerate(views)]
                 w = dist.gather(src_x, views, dst=self._global_rank(dst), group=self._xg, async_op=async_op)
             works = [w] if async_op and w is not None else []
         elif peer_equal:
@@ -625,7 +631,7 @@ class ShardedRayMeshIntersector:
         key = (tuple(shape), dtype, str(device))
         t = self._scratch_bufs.get(key)
         if t is None:
-            t = self._scratch_bufs[key] = torch.empty(shape, dtype=dtype, device=device)
+            t = self._scratch_bufs[key] = _new_output(shape, dtype, device)
         return t
 
     def _global_rank(self, r: int) -> int:
@@ -644,7 +650,7 @@ class ShardedRayMeshIntersector:
         want = dst is None or self.rank == dst
         pad = torch.zeros((m, *src.shape[1:]), dtype=src.dtype, device=src.device)
         pad[:sizes[self.rank]].copy_(src)
-        bufs = [torch.empty_like(pad) for _ in range(self.world)] if want else None
+        bufs = [_new_output(pad.shape, pad.dtype, pad.device) for _ in range(self.world)] if want else None
         if dst is None:
             dist.all_gather(bufs, pad, group=self._xg)
         else:
@@ -834,10 +840,10 @@ class ShardedRayMeshIntersector:
                     # earlier would spin on CUs through the whole trace.
                     rb = [(ra, rz) if r != rank else (ra, ra) for r, (ra, rz) in enumerate(cb)]
                     if empty is None:
-                        empty = torch.empty((0, *rec_shape), dtype=torch.int32, device=dev)
+                        empty = _new_output((0, *rec_shape), torch.int32, dev)
                     works = self._exchange_recv_only(empty, packed_all, rb, cb, dst)
                 else:
-                    src = mine[a:z] if m > 0 else torch.empty((0, *rec_shape), dtype=torch.int32, device=dev)
+                    src = mine[a:z] if m > 0 else _new_output((0, *rec_shape), torch.int32, dev)
                     works = self._exchange_send(src, packed_all, cb, dst)
             else:
                 works = []
