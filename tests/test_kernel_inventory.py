@@ -23,6 +23,9 @@ CAPS = "test_gpu_kernel_matrix.py::test_multi_hit_lists_match_the_oracle_at_ever
 CAP_EDGES = "test_gpu_kernel_matrix.py::test_multi_hit_cap_range_and_ray_base"
 SCANS = "test_gpu_kernel_matrix.py::test_scans_match_an_int64_cumsum"
 COMPACTION = "test_gpu_kernel_matrix.py::test_compact_closest_with_a_ray_base"
+# ---- the same flavours on rays at the ends of the float range (tests/test_gpu_hostile_rays.py): non-finite, zero, denormal and
+# 3e38 components, origins at 2^60 ... 3.4e38, whole waves of invalid rays -- the oracle's bits and rules that need no oracle
+HOSTILE = "test_gpu_hostile_rays.py::test_flavour_on_hostile_rays"
 # ---- older tests ----------------------------------------------------------------------------------------------------------
 BUILDER = "test_gpu_parity.py::test_builder_invariants_and_host_traversal_of_gpu_tree"
 UPDATE = "test_gpu_parity.py::test_update_raw_rebuilds"
@@ -54,34 +57,34 @@ for q in (0, 1, 2):
                   "false, true, 0, false, false", "false, true, 0, true, false",             # compact / deep plain
                   "false, true, 1, false, false", "false, true, 1, true, false",             # stealing on exact nodes
                   "false, true, 1, false, true", "false, true, 1, true, true"):              # stealing on grid nodes
-        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX,)
+        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX, HOSTILE)
     INVENTORY[f"void k_query_direct<{q}, true, false, 0, false, false>"] = STATS_ONLY
     # the stealing grid-node launch that carries the deferred sort of the learned order: <Q, DEEP, ...>
-    INVENTORY[f"void k_query_direct_sort<{q}, false, true, true>"] = (MATRIX,)
-    INVENTORY[f"void k_query_direct_sort<{q}, true, true, true>"] = (MATRIX,)
+    INVENTORY[f"void k_query_direct_sort<{q}, false, true, true>"] = (MATRIX, HOSTILE)
+    INVENTORY[f"void k_query_direct_sort<{q}, true, true, true>"] = (MATRIX, HOSTILE)
 for q in (3, 4):
     for flags in ("false, false, 2, false, false", "false, true, 2, false, false", "false, true, 2, true, false"):
-        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX, CAPS) if q == 4 else (MATRIX,)
+        INVENTORY[f"void k_query_direct<{q}, {flags}>"] = (MATRIX, HOSTILE, CAPS) if q == 4 else (MATRIX, HOSTILE)
     INVENTORY[f"void k_query_direct<{q}, true, false, 2, false, false>"] = STATS_ONLY
 # the stealing count launch <COMPACT, DEEP> and its sort-carrying form
 for flags in ("false, false", "true, false", "true, true"):
-    INVENTORY[f"void k_query_count_steal<{flags}>"] = (MATRIX,)
-INVENTORY["void k_query_count_steal_sort<false, true>"] = (MATRIX,)
-INVENTORY["void k_query_count_steal_sort<true, true>"] = (MATRIX,)
+    INVENTORY[f"void k_query_count_steal<{flags}>"] = (MATRIX, HOSTILE)
+INVENTORY["void k_query_count_steal_sort<false, true>"] = (MATRIX, HOSTILE)
+INVENTORY["void k_query_count_steal_sort<true, true>"] = (MATRIX, HOSTILE)
 for q in range(5):
-    INVENTORY[f"void k_query_direct_wide<{q}>"] = (MATRIX,)
+    INVENTORY[f"void k_query_direct_wide<{q}>"] = (MATRIX, HOSTILE)
 # streaming launches <Q, 32-bit offsets, block, DEEP> (no location query: it keeps the direct launch)
 for q in range(4):
     for flags in ("false, 128, false", "true, 128, false", "true, 128, true"):
-        INVENTORY[f"void k_query_stream<{q}, {flags}>"] = (MATRIX,)
+        INVENTORY[f"void k_query_stream<{q}, {flags}>"] = (MATRIX, HOSTILE)
     INVENTORY[f"void k_query_stream_stats<{q}, false, 128, false>"] = STATS_ONLY
-    INVENTORY[f"void k_query_wide<{q}>"] = (MATRIX, WIDE)
+    INVENTORY[f"void k_query_wide<{q}>"] = (MATRIX, HOSTILE, WIDE)
 INVENTORY.update({
     # multi-hit lists: the two-pass fill (cap <= 8 / 16 / 32) and the fill from the fused traversal's slots
     "void k_location<8>": (CAPS, CAP_EDGES),
     "void k_location<16>": (CAPS,),
     "void k_location<32>": (CAPS,),
-    "k_fill_list": (CAPS, CAP_EDGES, MATRIX),
+    "k_fill_list": (CAPS, CAP_EDGES, MATRIX, HOSTILE),
     "void k_scan_partial<int>": (SCANS, CAPS),
     "void k_scan_final<int>": (SCANS, CAPS),
     "void k_scan_partial<unsigned char>": (SCANS, COMPACTION),
@@ -109,7 +112,7 @@ INVENTORY.update({
     "k_qframe_box": (REFIT, REFIT_STRUCT, REFIT_HANDLES),
     "k_refit_nodes_round": (REFIT, REFIT_STRUCT, REFIT_HANDLES), "k_update_boxes": (REFIT, REFIT_STRUCT, REFIT_HANDLES),
     # the 8-wide nodes are built on first use by the launches that walk them
-    "k_wide_mark": (WIDE, MATRIX), "k_wide_emit": (WIDE, MATRIX),
+    "k_wide_mark": (WIDE, MATRIX, HOSTILE), "k_wide_emit": (WIDE, MATRIX, HOSTILE),
     "k_replica_hash": (REPLICA,),
     # scheduling: these decide only the ORDER in which blocks run; the launches behind them are compared with the oracle
     "k_probe_coherence": (PROBE,),
