@@ -61,8 +61,12 @@ template <int Q, bool STATS, bool COMPACT, bool DEEP = false, bool QN = false>
 __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray& r, bool go,
                                                     tr_result& res, tr_counters* cnt,
                                                     const tr_ring ring, int32_t* wl, int lane,
-                                                    uint32_t steal_min) {
-    typedef typename tr_word<COMPACT, DEEP>::T W;
+                                                    uint32_t steal_min, bool& lost) {
+    // the grid-node launch walks with the plain far-child stack (tr_plain_w, tr_bvh.h: no trail words, so DEEP is the same
+    // code); the launch on the exact nodes (option grid_nodes = 0) keeps the dense stack and never loses a child
+    constexpr bool PLAIN = QN;
+    typedef typename std::conditional<PLAIN, tr_plain_w, typename tr_word<COMPACT, DEEP>::T>::type W;
+    lost = false;
     tr_result_init(res);
     tr_topk<1> top;
     tr_state_t<W> fs;
@@ -103,7 +107,12 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     lds_i32* const lw = (lds_i32*)wl;
     lds_i32* const list = lw;                    // [64] donor lane of pair k
     lds_i32* const xnode = lw + 64;              // [64] node handed over by donor lane
-    lds_i32* const xdepth = lw + 128;            // [64] its depth
+    // [64] dense stack: the depth of the node handed over.  Plain stack: per lane, bits 0-7 = entries this lane has given
+    // away since its stack was last empty (`bot`, tr_plain_give), bit 8 = a lane that worked on THIS lane's ray lost a
+    // far child (set by that lane when it hands its results in)
+    lds_i32* const xdepth = lw + 128;
+    int32_t* const xflags = wl + 128;
+    if constexpr (PLAIN) xdepth[lane] = 0;
     // per-ray accumulators at the owner's index: partial results are deposited whenever a lane
     // finishes a piece of work (before it takes the next one) and once more at the end
     constexpr int ACC = 192;
@@ -113,6 +122,9 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     lds_u64* const vkeys = (lds_u64*)(lw + ACC);
     lds_i32* const vslots = lw + ACC + 128;
     auto deposit = [&]() {
+        if constexpr (PLAIN) {
+            if (tr_plain_lost(fs.sp)) atomicOr(&xflags[owner], 0x100);
+        }
         if (Q == TR_Q_COUNT) {
             if (res.count) atomicAdd(&sum[owner], res.count);
         } else if (Q == TR_Q_ANY) {
@@ -172,8 +184,15 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
         const unsigned long long idle = __ballot(done);
         if (idle == ~0ull) break;
         if (__popcll(idle) >= TR_STEAL_IDLE) {
-            const W cand = fs.trail & fs.owned;      // owed far children that are in the stack
-            const bool can_give = !done && cand != 0 && trip >= steal_min;
+            uint32_t bot = 0;
+            bool has_far;                            // owed far children that are in the stack
+            if constexpr (PLAIN) {
+                bot = (uint32_t)xdepth[lane] & 0xffu;
+                has_far = tr_plain_can_give(fs.sp, bot);
+            } else {
+                has_far = (fs.trail & fs.owned) != 0;
+            }
+            const bool can_give = !done && has_far && trip >= steal_min;
             const unsigned long long donors = __ballot(can_give);
             const int ni = __popcll(idle), nd = __popcll(donors);
             const int np = ni < nd ? ni : nd;
@@ -187,7 +206,15 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                 const int drank = lane_rank(donors), irank = lane_rank(idle);
                 const bool give = can_give && drank < np;
                 int gnode = 0, gdepth = 0;
-                if (give) {
+                (void)gdepth;
+                if constexpr (PLAIN) {
+                    if (give) {
+                        // the shallowest = the bottom of the stack; -1 takes its place (tr_plain_give)
+                        gnode = tr_plain_give(ring, bot);
+                        list[drank] = lane; xnode[lane] = gnode;
+                        atomicAdd(&xflags[lane], 1);
+                    }
+                } else if (give) {
                     // the shallowest = the bottom of the stack; its owned bit stays behind and keeps the others' slots (tr_ring)
                     uint32_t j;
                     gnode = tr_ring_get(ring, tr_bottom_slot<W>(fs.trail, fs.owned, j));
@@ -221,7 +248,8 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                     owner = own2;
                     tr_state_init(fs);
                     fs.node = xnode[src];
-                    fs.depth = (uint32_t)xdepth[src];
+                    if constexpr (PLAIN) atomicAnd(&xflags[lane], 0x100);      // an empty stack: nothing given away
+                    else fs.depth = (uint32_t)xdepth[src];
                     tr_set_best_t(res, bt);
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -245,6 +273,9 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                 res.best_slot = vslots[lane];
             }
         }
+        if constexpr (PLAIN) lost = (xdepth[lane] & 0x100) != 0;
+    } else if constexpr (PLAIN) {
+        lost = tr_plain_lost(fs.sp);
     }
     return split;
 }
@@ -280,6 +311,31 @@ __device__ __forceinline__ void process_ray(const tr_bvh_view& b, const RayFetch
     if (in_range) write_result<Q>(b, out, i, r, res);
 }
 
+// The rays of a wave whose plain far-child stack lost a child (tr_plain_push; on the lane that owns the ray or on a thief):
+// traversed once more, from the best hit so far, by the stackless walk over the exact nodes (tr_traverse_more).  A real call
+// behind a branch marked as unlikely, like the float64 part of the hit predicate (tr_drain_exact<COLD>): what it needs is
+// saved around the call and it puts nothing into the trips.  Everything arrives by value -- a pointer to the caller's view or
+// ray would pin those to scratch for the whole kernel.
+template <int Q>
+__device__ __attribute__((noinline)) tr_result retraverse_lost(const tr_node* nodes, const tr_link* links, const tr_tri* tris,
+                                                               float b0, float b1, float b2, float s0, float s1, float s2,
+                                                               float ox, float oy, float oz, float dx, float dy, float dz,
+                                                               float best_t, int32_t best_face, int32_t best_slot) {
+    tr_bvh_view v;
+    v.nodes = nodes; v.links = links; v.tris = tris; v.num_tris = 2; v.qnodes = nullptr; v.frame_dev = nullptr;
+    v.frame.base[0] = b0; v.frame.base[1] = b1; v.frame.base[2] = b2;
+    v.frame.scale[0] = s0; v.frame.scale[1] = s1; v.frame.scale[2] = s2;
+    tr_result res;
+    res.best_t = best_t; res.best_face = best_face; res.best_slot = best_slot; res.count = 0;
+    tr_ray r;
+    if (tr_ray_setup_a(r, v.frame, ox, oy, oz, dx, dy, dz)) {
+        tr_topk<1> top;
+        tr_counters* nc = nullptr;
+        tr_traverse_more<Q, 1, false>(v, r, res, top, nc);
+    }
+    return res;
+}
+
 template <int Q, bool STATS, bool COMPACT, bool DEEP = false, bool QN = false>
 __device__ __forceinline__ void process_ray_steal(const tr_bvh_view& b, const RayFetch& rf,
                                                   const QueryOut& out, int64_t i, bool in_range,
@@ -290,12 +346,24 @@ __device__ __forceinline__ void process_ray_steal(const tr_bvh_view& b, const Ra
     tr_ray r;
     const bool valid = tr_ray_setup_q(r, b.frame, o[0], o[1], o[2], d[0], d[1], d[2]) && in_range;
     tr_result res;
-    bool split = false;
-    if (b.num_tris >= 2) split = wave_traverse_steal<Q, STATS, COMPACT, DEEP, QN>(b, r, valid, res, cnt, ring, wl, (int)(threadIdx.x & 63), steal_min);
+    bool split = false, lost = false;
+    if (b.num_tris >= 2) split = wave_traverse_steal<Q, STATS, COMPACT, DEEP, QN>(b, r, valid, res, cnt, ring, wl, (int)(threadIdx.x & 63), steal_min, lost);
     else brute_one<Q>(b, r, valid, res);   // no hierarchy below two triangles
     if (split && in_range) {   // this lane may hold another lane's ray now: take its own again
         fetch_ray(rf, i, o, d);
         tr_ray_setup_a(r, b.frame, o[0], o[1], o[2], d[0], d[1], d[2]);
+    }
+    if constexpr (QN) {
+        lost = lost && valid;
+        if (__builtin_expect(TR_WAVE_ANY(lost), 0)) {
+            if (lost) {
+                // (the ray is fetched again: kept from the prologue it would cost the trips six registers)
+                fetch_ray(rf, i, o, d);
+                res = retraverse_lost<Q>(b.nodes, b.links, b.tris, b.frame.base[0], b.frame.base[1], b.frame.base[2],
+                                         b.frame.scale[0], b.frame.scale[1], b.frame.scale[2], o[0], o[1], o[2], d[0], d[1], d[2],
+                                         res.best_t, res.best_face, res.best_slot);
+            }
+        }
     }
     if (in_range) write_result<Q>(b, out, i, r, res);
 }
@@ -689,10 +757,14 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
         // 2x32; lgh in bits 28-29 of the argument) instead of 64 pixels of one row
         const int lgh = (tile_w >> 28) & 3, lgw = 6 - lgh;
         const int64_t width = tile_w & 0x0fffffff;
-        const int64_t tile = i >> 6, tpr = width >> lgw;
-        const int lane = (int)(i & 63);
-        const int64_t ty = tile / tpr, tx = tile - ty * tpr;
-        i = ((ty << lgh) + (lane >> lgw)) * width + (tx << lgw) + (lane & ((1 << lgw) - 1));
+        // the tile index and its row / column are the same for the whole wave: scalar arithmetic in 32 bits (a launch has
+        // fewer than 2^31 blocks of two tiles; the width is below 2^28), not a 64-bit division per lane
+        static_assert(BS % 64 == 0, "a wave is one tile");
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const uint32_t tile = (uint32_t)blk * (uint32_t)(BS / 64) + wave, tpr = (uint32_t)(width >> lgw);
+        const int lane = (int)(threadIdx.x & 63);
+        const uint32_t ty = tile / tpr, tx = tile - ty * tpr;
+        i = (((int64_t)ty << lgh) + (lane >> lgw)) * width + ((int64_t)tx << lgw) + (lane & ((1 << lgw) - 1));
     }
     tr_counters cnt = {0, 0, 0};
     if (MODE == 4) {

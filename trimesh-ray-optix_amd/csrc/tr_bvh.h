@@ -536,6 +536,62 @@ TR_HD void tr_state_init(tr_state_t<W>& st) {
     st.p0 = -1; st.p1 = -1; st.p2 = -1; st.pe = -1;
 }
 
+// ---- plain far-child stack (round 8): the stealing closest / first / any launch on the grid nodes -------------------
+// The far children are a LIFO, and trail / owned / depth and the rank arithmetic above exist only to find an entry again
+// by climbing when the TR_RING words did not hold it, and to let the hand-over take the bottom entry: about a third of
+// the VALU instructions of a trip without a leaf block, on a kernel whose vector pipes are 92 % busy, for an overflow
+// that no ray of an image of a closed surface ever has.  This walk keeps the same words as a stack with a stack
+// pointer and nothing else:
+//   sp = 2 * (slots in use) | lost.   push: sp < 2 * TR_RING ? store at slot sp / 2, sp += 2 : sp |= 1 (the child is
+//   NOT recorded and the sticky `lost` bit says that this lane's walk is no longer complete);   pop: sp < 2 ? the walk
+//   is over (node = -1) : sp -= 2, load slot sp / 2.
+// Order, cull limit, leaf FIFO and alternation are those of the dense stack: without an overflow the walk visits exactly
+// the same nodes and tests exactly the same leaves.  A ray with a lost child (on any lane that worked on it) is
+// traversed AGAIN after the wave's loop by the stackless walk over the exact nodes (tr_traverse_more), starting from the
+// best hit found so far: closest / first are a lexicographic minimum over candidates and any is an OR, so the order of
+// the candidates does not matter and the result is the same bits.  Cold, correct, not fast.
+// Hand-over (wave_traverse_steal): the donor gives its SHALLOWEST entry, slot `bot` -- the number of entries it has
+// given away since its stack was last empty, which the kernel keeps in LDS, outside the trips -- and leaves -1 in its
+// place (tr_plain_give).  Far children are internal nodes (>= 0), so when the walk pops down to a given-away slot it
+// reads -1: exactly "nothing left", because everything below it was given away before it.  Given-away slots stay in
+// use until the lane starts another walk: a donor's stack is shorter by its gifts, and a push that does not fit is
+// lost like any other.
+struct tr_plain_w {};      // in place of the trail word type: selects this walk in tr_fused_body and the state below
+template <>
+struct tr_state_t<tr_plain_w> {
+    int32_t node;     // next internal node to visit, -1 = nothing left
+    uint32_t sp;      // 2 * slots in use | lost
+    int32_t p0, p1, p2;
+    int32_t pe;
+};
+typedef tr_state_t<tr_plain_w> tr_pstate;
+TR_HD void tr_state_init(tr_pstate& st) {
+    st.node = 0; st.sp = 0;
+    st.p0 = -1; st.p1 = -1; st.p2 = -1; st.pe = -1;
+}
+TR_HD void tr_plain_push(const tr_ring ring, uint32_t& sp, int32_t node) {
+    if (sp < 2u * TR_RING) {
+        tr_ring_put(ring, sp >> 1, node);
+        sp += 2u;
+    } else {
+        sp |= 1u;
+    }
+}
+TR_HD int32_t tr_plain_pop(const tr_ring ring, uint32_t& sp) {
+    if (sp < 2u) return -1;
+    sp -= 2u;
+    return tr_ring_get(ring, sp >> 1);
+}
+TR_HD bool tr_plain_lost(uint32_t sp) { return (sp & 1u) != 0; }
+// entries a lane could still give away, and the hand-over of the shallowest of them (see above)
+TR_HD bool tr_plain_can_give(uint32_t sp, uint32_t bot) { return (sp >> 1) > bot; }
+TR_HD int32_t tr_plain_give(const tr_ring ring, uint32_t& bot) {
+    const int32_t node = tr_ring_get(ring, bot);
+    tr_ring_put(ring, bot, -1);
+    bot++;
+    return node;
+}
+
 template <typename W>
 TR_HD bool tr_pending(const tr_state_t<W>& st) { return st.p0 >= 0 || st.p1 >= 0; }
 template <typename W>
@@ -819,7 +875,19 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
         st.p1 = hb ? xi : (two ? i1 : -1);
         st.p2 = (hb && two) ? i1 : -1;
     }
-    if (go) {
+    if constexpr (std::is_same<W, tr_plain_w>::value) {
+        // the plain stack (tr_plain_push): no trail, no depth, no climb
+        if (go) {
+            if (h0 || h1) {
+                const bool both = h0 && h1;
+                const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
+                if (both) tr_plain_push(ring, st.sp, swap ? c0 : c1);
+                st.node = swap ? c1 : c0;
+            } else {
+                st.node = tr_plain_pop(ring, st.sp);
+            }
+        }
+    } else if (go) {
         if (h0 || h1) {
             const bool both = h0 && h1;
             const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
@@ -1043,6 +1111,22 @@ TR_HD void tr_traverse_unordered(const tr_bvh_view& b, const tr_ray& r, bool val
     while (!tr_udone(st)) {
         const bool cn = tr_ucan_node(st);
         tr_unord_step<Q, K, STATS, false, uint64_t>(b, r, cn, !cn, st, res, top, cnt, ring, lq);
+        TR_CONVERGE();
+    }
+}
+
+// The second traversal of a ray whose plain stack lost a far child (tr_plain_push): the whole hierarchy once more with
+// the stackless walk over the exact nodes (no ring: every far child is found by climbing), `res` keeping what the first
+// traversal found -- its best hit is the starting bound (closest / first), a hit ends it at once (any).  `r` needs the
+// constants of tr_ray_setup_a only.
+template <int Q, int K, bool STATS>
+TR_HD void tr_traverse_more(const tr_bvh_view& b, const tr_ray& r, tr_result& res, tr_topk<K>& top, tr_counters* cnt) {
+    if (Q == TR_Q_ANY && res.best_face >= 0) return;
+    tr_state st;
+    tr_state_init(st);
+    while (!tr_done(st)) {
+        if (tr_pending(st)) tr_leaf_step<Q, K, STATS>(b, r, st, res, top, cnt);
+        else tr_node_step<Q, STATS>(b, r, st, res, cnt, tr_ring{nullptr, 0});
         TR_CONVERGE();
     }
 }
