@@ -602,3 +602,78 @@ def rccl_available() -> bool:
 def _check_rccl(rc: int):
     if rc != 0:
         raise RuntimeError("libtriro_rccl: " + (get_rccl_module().tr_rccl_last_error() or b"?").decode())
+
+
+# --- contains_points as one launch (include/triro_points.h, csrc/points.hip) ------------------------------------------
+_POINTS_LIB_NAME = "libtriro_points.so"
+POINTS_ABI_VERSION = 1    # TR_POINTS_ABI_VERSION of include/triro_points.h
+_points_module = None
+
+# every symbol include/triro_points.h declares: (restype, argtypes)
+POINTS_ABI = {
+    "tr_points_abi_version": (_int, []),
+    "tr_contains_addressing": (_int, [_vp]),
+    "tr_contains_points": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+}
+
+
+def points_library_path() -> str:
+    return os.environ.get("TRIRO_POINTS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _POINTS_LIB_NAME)
+
+
+def get_points_module():
+    """libtriro_points.so.  Raises when it is not built or does not match this binding."""
+    global _points_module
+    if _points_module is None:
+        get_module()                       # libtriro_hip.so first: the points library links against it
+        path = points_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build())")
+        lib = C.CDLL(path)
+        for name, (res, args) in POINTS_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_points_abi_version() != POINTS_ABI_VERSION:
+            raise RuntimeError(f"libtriro_points.so ABI version {lib.tr_points_abi_version()} != {POINTS_ABI_VERSION} expected by this binding")
+        _points_module = lib
+    return _points_module
+
+
+def contains_addressing(accel_structure) -> int:
+    """the instantiation of k_contains_points a call on this handle takes now: 0 generic, 1 compact, 2 deep"""
+    return int(get_points_module().tr_contains_addressing(_handle(accel_structure)))
+
+
+def contains_points_native(accel_structure, points, direction, box_lo, box_hi, want_counts=False):
+    """tr_contains_points: (inside bool[n], broken bool[n], counts int32[2, n] or None, summary int64[2] = {points in the
+    box, broken points}) for float32 points [n, 3] and 3-float device tensors direction / box_lo / box_hi (both boxes None:
+    no box test).  Nothing is synchronised: the caller reads `summary` when it needs it."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
+            points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    dev = points.device
+    handle = _handle(accel_structure, points)
+    points = points.contiguous()
+    small = [direction, box_lo, box_hi]
+    if (box_lo is None) != (box_hi is None):
+        raise ValueError("box_lo and box_hi must both be given or both be None")
+    for k, t in enumerate(small):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.numel() != 3:
+            raise ValueError("direction, box_lo and box_hi must be tensors of 3 elements")
+        small[k] = t.to(device=dev, dtype=torch.float32).contiguous()
+    direction, box_lo, box_hi = small
+    n = points.shape[0]
+    inside = _new_output((n,), torch.bool, dev)
+    broken = _new_output((n,), torch.bool, dev)
+    counts = _new_output((2, n), torch.int32, dev) if want_counts else None
+    summary = _new_output((2,), torch.int64, dev)
+    with torch.cuda.device(dev):
+        _check(get_points_module().tr_contains_points(
+            handle, points.data_ptr(), n, direction.data_ptr(),
+            box_lo.data_ptr() if box_lo is not None else None, box_hi.data_ptr() if box_hi is not None else None,
+            inside.data_ptr(), broken.data_ptr(), counts.data_ptr() if counts is not None else None,
+            summary.data_ptr(), None, _stream_ptr(dev)))
+    return inside, broken, counts, summary

@@ -16,12 +16,17 @@ Every method keeps the reference's name, arguments, return order, shapes and dty
 from __future__ import annotations
 
 import ctypes as C
+import os
+import warnings
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 import triro.backend.ops as hops
+
+
+_points_warned = False      # (OptixAccelStructureWrapper._init_points)
 
 
 def _default_device() -> torch.device:
@@ -194,11 +199,61 @@ class RayMeshIntersector:
             return tri_c, ray_idx, loc_c
         return tri_c, ray_idx
 
+    # contains_points goes through libtriro_points.so (one launch, include/triro_points.h) when it can; False: always the
+    # torch statements around intersects_count (_contains_points_torch)
+    native_contains = True
+
+    _DEFAULT_DIRECTION = (0.4395064455, 0.617598629942, 0.652231566745)      # ray_optix.py:245-247
+
+    def _takes_native_contains(self, points, check_direction) -> bool:
+        if not self.native_contains:
+            return False
+        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and
+                points.dim() == 2 and points.shape[1] == 3 and points.device.index == self.as_wrapper.device_index):
+            return False
+        if check_direction is not None and not (isinstance(check_direction, torch.Tensor) and check_direction.numel() == 3):
+            return False
+        # bounds that are not float32 (a box set through the setter) keep the torch statements, which compare in the
+        # bounds' own type: the kernel would compare against their float32 roundings
+        if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.numel() == 3 for t in self.mesh_aabb):
+            return False
+        # only a library that was never built falls back quietly; one that is there and does not load or match raises
+        if not os.path.exists(hops.points_library_path()):
+            return False
+        hops.get_points_module()
+        return True
+
     def contains_points(self, points, check_direction: Optional[torch.Tensor] = None, _retry_direction=None):
-        """ray_optix.py:231-279, statement for statement (including its two quirks: points
-        must be [n, 3]; with an explicit `check_direction` and unresolved points the
-        all-False `contains` is returned, :272-279).  `_retry_direction` replaces the
-        reference's `torch.rand(3) - 0.5` (:273) when a deterministic retry is wanted."""
+        """ray_optix.py:231-279 (including its two quirks: points must be [n, 3]; with an explicit
+        `check_direction` and unresolved points the all-False `contains` is returned, :272-279).
+        `_retry_direction` replaces the reference's `torch.rand(3) - 0.5` (:273) when a deterministic
+        retry is wanted.  Float32 points on the acceleration structure's GPU take one fused launch
+        (tr_contains_points: both rays of a point in one lane, the decision written by the kernel, one
+        host read of two totals); anything else takes _contains_points_torch.  Same results."""
+        if not self._takes_native_contains(points, check_direction):
+            return self._contains_points_torch(points, check_direction, _retry_direction)
+        dev = points.device
+        if check_direction is None:
+            direction = torch.tensor(self._DEFAULT_DIRECTION, dtype=torch.float32, device=dev)
+        else:
+            direction = check_direction.to(device=dev, dtype=torch.float32).reshape(3)
+        lo, hi = (t.reshape(3) for t in self.mesh_aabb)
+        inside, broken, _, summary = hops.contains_points_native(self.as_wrapper, points, direction, lo, hi)
+        in_box, unresolved = summary.tolist()          # the one host read
+        if in_box == 0:                                 # :241-242, before any retry direction is drawn
+            return torch.zeros(points.shape[:-1], dtype=torch.bool, device=dev)
+        if unresolved == 0:                             # :269-270
+            return inside
+        if check_direction is None:                     # :272-278
+            new_direction = (_retry_direction if _retry_direction is not None else (torch.rand(3) - 0.5)).to(dev)
+            inside[broken] = self.contains_points(points[broken], new_direction)
+            return inside
+        return torch.zeros(points.shape[:-1], dtype=torch.bool, device=dev)      # :279, the all-False `contains`
+
+    def _contains_points_torch(self, points, check_direction: Optional[torch.Tensor] = None, _retry_direction=None):
+        """ray_optix.py:231-279, statement for statement, as torch operations around ONE intersects_count launch on 2n
+        materialised rays: what every call ran before libtriro_points.so, and what a call that does not meet the
+        conditions of the native route still runs."""
         dev = points.device
         contains = torch.zeros(points.shape[:-1], dtype=torch.bool, device=dev)
         inside_aabb = ~((~(points > self.mesh_aabb[0])).any(dim=1) | (~(points < self.mesh_aabb[1])).any(dim=1))
@@ -308,6 +363,22 @@ class OptixAccelStructureWrapper:
                                              faces.shape[0], stream, C.byref(handle)))
                 self._inner = handle.value
         self.device_index = int(self.info()["device"])     # the GPU that owns the arena, as the library sees it
+        self._init_points()
+
+    def _init_points(self):
+        """the init path of libtriro_points.so on this handle's device (tr_contains_addressing): afterwards contains_points
+        allocates nothing, so even its first call can be captured in a graph.  Building or loading a handle never fails
+        over that library: one that is present but does not load or match is reported once here, and raises from
+        contains_points, the only method that needs it."""
+        if not os.path.exists(hops.points_library_path()):
+            return
+        try:
+            hops.contains_addressing(self)
+        except (RuntimeError, OSError, AttributeError) as e:
+            global _points_warned
+            if not _points_warned:
+                _points_warned = True
+                warnings.warn(f"libtriro_points.so is present but unusable ({e}); contains_points will raise", RuntimeWarning)
 
     def refit(self, vertices: torch.Tensor, faces: torch.Tensor):
         if not self._inner:
@@ -335,6 +406,7 @@ class OptixAccelStructureWrapper:
                                                              torch.cuda.current_stream(device).cuda_stream, C.byref(handle)))
         self._inner = handle.value
         self.device_index = self.info()["device"]
+        self._init_points()
 
     def replica_hash(self) -> int:
         h = C.c_uint64(0)
