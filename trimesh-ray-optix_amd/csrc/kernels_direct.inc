@@ -183,7 +183,9 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
         const bool done = tr_done(fs);
         const unsigned long long idle = __ballot(done);
         if (idle == ~0ull) break;
-        if (__popcll(idle) >= TR_STEAL_IDLE) {
+        // the wave-uniform test first: below the threshold nobody gives, and the lanes' look at their stacks (an LDS round
+        // trip for `bot`) would decide nothing -- a coherent wave of the headline is over after 48 trips on average
+        if (__popcll(idle) >= TR_STEAL_IDLE && trip >= steal_min) {
             uint32_t bot = 0;
             bool has_far;                            // owed far children that are in the stack
             if constexpr (PLAIN) {
@@ -192,7 +194,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             } else {
                 has_far = (fs.trail & fs.owned) != 0;
             }
-            const bool can_give = !done && has_far && trip >= steal_min;
+            const bool can_give = !done && has_far;
             const unsigned long long donors = __ballot(can_give);
             const int ni = __popcll(idle), nd = __popcll(donors);
             const int np = ni < nd ? ni : nd;

@@ -876,16 +876,18 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
         st.p2 = (hb && two) ? i1 : -1;
     }
     if constexpr (std::is_same<W, tr_plain_w>::value) {
-        // the plain stack (tr_plain_push): no trail, no depth, no climb
+        // the plain stack (tr_plain_push): no trail, no depth, no climb.  The descend path's select is written FIRST and for
+        // every lane, the pop's load into the same register behind it: with the pop in a branch of its own in front, the
+        // select overwrote a register with a load outstanding and the compiler made the whole wave wait for LDS (and for
+        // the push's store) in the middle of the body; now the popped node is waited for where the next trip needs it.
+        // KEEP THIS ORDER: an if / else of descend and pop computes the same and brings the wait back (headline +1.2 %,
+        // wait cycles per wave -3.5 %: DESIGN_experiments.md part R9, with the assembly of both forms)
         if (go) {
-            if (h0 || h1) {
-                const bool both = h0 && h1;
-                const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
-                if (both) tr_plain_push(ring, st.sp, swap ? c0 : c1);
-                st.node = swap ? c1 : c0;
-            } else {
-                st.node = tr_plain_pop(ring, st.sp);
-            }
+            const bool both = h0 && h1;
+            const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
+            if (both) tr_plain_push(ring, st.sp, swap ? c0 : c1);
+            st.node = swap ? c1 : c0;
+            if (!(h0 || h1)) st.node = tr_plain_pop(ring, st.sp);
         }
     } else if (go) {
         if (h0 || h1) {
