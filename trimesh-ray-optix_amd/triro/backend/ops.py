@@ -677,3 +677,62 @@ def contains_points_native(accel_structure, points, direction, box_lo, box_hi, w
             inside.data_ptr(), broken.data_ptr(), counts.data_ptr() if counts is not None else None,
             summary.data_ptr(), None, _stream_ptr(dev)))
     return inside, broken, counts, summary
+
+
+# --- closest_point as one launch (include/triro_nearest.h, csrc/nearest.hip) -------------------------------------------
+_NEAREST_LIB_NAME = "libtriro_nearest.so"
+NEAREST_ABI_VERSION = 1    # TR_NEAREST_ABI_VERSION of include/triro_nearest.h
+_nearest_module = None
+
+# every symbol include/triro_nearest.h declares: (restype, argtypes)
+NEAREST_ABI = {
+    "tr_nearest_abi_version": (_int, []),
+    "tr_nearest_stack_capacity": (_int, []),
+    "tr_closest_point": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+def nearest_library_path() -> str:
+    return os.environ.get("TRIRO_NEAREST_LIBRARY") or os.path.join(os.path.dirname(library_path()), _NEAREST_LIB_NAME)
+
+
+def get_nearest_module():
+    """libtriro_nearest.so.  Raises when it is not built or does not match this binding."""
+    global _nearest_module
+    if _nearest_module is None:
+        get_module()                       # libtriro_hip.so first: the nearest library links against it
+        path = nearest_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in NEAREST_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_nearest_abi_version() != NEAREST_ABI_VERSION:
+            raise RuntimeError(f"libtriro_nearest.so ABI version {lib.tr_nearest_abi_version()} != {NEAREST_ABI_VERSION} expected by this binding")
+        _nearest_module = lib
+    return _nearest_module
+
+
+def closest_point_native(accel_structure, points, stack_entries=0, want_closest=True, want_distance=True):
+    """tr_closest_point: (closest float32[n, 3] or None, distance float32[n] or None, tri int32[n]) for float32 points
+    [n, 3] on the handle's GPU.  stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).
+    Nothing is allocated by the library and nothing is synchronised."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
+            points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    lib = get_nearest_module()
+    dev = points.device
+    handle = _handle(accel_structure, points)
+    points = points.contiguous()
+    n = points.shape[0]
+    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
+    distance = _new_output((n,), torch.float32, dev) if want_distance else None
+    tri = _new_output((n,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_closest_point(handle, points.data_ptr(), n, closest.data_ptr() if closest is not None else None,
+                                    distance.data_ptr() if distance is not None else None, tri.data_ptr(),
+                                    int(stack_entries), _stream_ptr(dev)))
+    return closest, distance, tri

@@ -283,6 +283,42 @@ class RayMeshIntersector:
             contains[broken_mask] = self.contains_points(points[broken_mask], new_direction)
         return contains
 
+    # -- proximity (trimesh.proximity; not in the reference) ----------------------------------
+    def closest_point(self, points) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """trimesh.proximity.closest_point: (closest[*b,3] float32, distance[*b] float32, triangle_id[*b] int32) of
+        points [*b, 3], one launch of libtriro_nearest.so (tr_closest_point).  Distances are evaluated in float64 from
+        the float32 inputs; among triangles at exactly the same distance the smaller face index wins (trimesh leaves
+        that open).  A point with a non-finite component, or an empty mesh: (NaN, +Inf, -1).  Points are converted to
+        contiguous float32 on the acceleration structure's GPU; a tensor on another GPU raises."""
+        dev = self.mesh_vertices.device
+        if isinstance(points, torch.Tensor):
+            if not points.is_cuda:
+                raise ValueError("points must reside on a GPU (cuda/HIP) device")
+            if points.device != dev:
+                raise ValueError(f"points are on {points.device} but the acceleration structure lives on {dev}; "
+                                 f"move the points or build the intersector on that device")
+        p = _to_device_tensor(points, torch.float32, dev)
+        if p.dim() < 1 or p.shape[-1] != 3:
+            raise ValueError(f"points must have shape [*b, 3], got {tuple(p.shape)}")
+        b = p.shape[:-1]
+        closest, distance, tri = hops.closest_point_native(self.as_wrapper, p.reshape(-1, 3))
+        return closest.reshape(*b, 3), distance.reshape(b), tri.reshape(b)
+
+    def signed_distance(self, points, check_direction: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
+        POSITIVE inside, negative elsewhere (trimesh's convention).  `check_direction` is contains_points' argument."""
+        dev = self.mesh_vertices.device
+        if isinstance(points, torch.Tensor) and not points.is_cuda:
+            raise ValueError("points must reside on a GPU (cuda/HIP) device")
+        p = _to_device_tensor(points, torch.float32, dev)
+        if p.dim() < 1 or p.shape[-1] != 3:
+            raise ValueError(f"points must have shape [*b, 3], got {tuple(p.shape)}")
+        b = p.shape[:-1]
+        flat = p.reshape(-1, 3)
+        _, distance, _ = hops.closest_point_native(self.as_wrapper, flat, want_closest=False)
+        inside = self.contains_points(flat, check_direction)      # (keeps its [n, 3] quirk)
+        return torch.where(inside, distance, -distance).reshape(b)
+
     # -- extras (not in the reference) -------------------------------------------------------
     def bvh_info(self) -> dict:
         return self.as_wrapper.info()
