@@ -7,8 +7,11 @@
  *              equal d2 the smaller face index wins, whatever the traversal order
  *   closest  = the float64 closest point on that triangle, rounded to float32
  *   distance = (float)sqrt(d2), the square root in float64; +Inf beyond the float range
- *   a point with a non-finite component, or a mesh of zero triangles: tri = -1, distance = +Inf, closest = NaN
- * Zero-area triangles are the segment or point they degenerate to.  Finite inputs never give NaN.
+ *   a point with a non-finite component, a mesh of zero triangles or one without an active triangle: tri = -1,
+ *   distance = +Inf, closest = NaN
+ * Zero-area triangles are the segment or point they degenerate to.  Finite inputs never give NaN.  A triangle with a NaN
+ * or an infinite coordinate is INACTIVE: it offers no candidate and is never returned, exactly as no ray query of
+ * libtriro_hip.so ever hits it; the other triangles answer as if it were not there.
  *
  * Conventions are those of triro_hip.h: d_* are DEVICE pointers on the device of the handle, work is enqueued on
  * `stream`, the return value is a tr_status and tr_last_error() (of libtriro_hip.so) has the message.  The library links

@@ -197,8 +197,9 @@ static inline float pad_(float x) { return fabsf(x) * TR_PAD_REL + TR_PAD_ABS; }
 static inline void tri_box_padded(const float *a, const float *b, const float *c, float *lo,
                                   float *hi) {
     for (int i = 0; i < 3; i++) {
-        float l = minf_(minf_(a[i], b[i]), c[i]);
-        float h = maxf_(maxf_(a[i], b[i]), c[i]);
+        /* fminf / fmaxf as the product's tr_tri_box: a NaN coordinate is ignored (all three NaN: a NaN bound) */
+        float l = fminf(fminf(a[i], b[i]), c[i]);
+        float h = fmaxf(fmaxf(a[i], b[i]), c[i]);
         lo[i] = l - pad_(l);
         hi[i] = h + pad_(h);
     }
@@ -353,6 +354,8 @@ static int cmp_cent(const void *x, const void *y) {
     float a = ((const cent_t *)x)->c[g_axis], b = ((const cent_t *)y)->c[g_axis];
     if (a < b) return -1;
     if (a > b) return 1;
+    /* a NaN centre (a NaN or an Inf - Inf box) sorts behind every number: the order stays total, any split is a valid BVH */
+    if ((a != a) != (b != b)) return (a != a) ? 1 : -1;
     int32_t ia = ((const cent_t *)x)->id, ib = ((const cent_t *)y)->id;
     return (ia > ib) - (ia < ib);
 }
@@ -375,10 +378,12 @@ static int32_t build_rec(omesh_t *m, cent_t *cents, int32_t first, int32_t count
         float lo[3], hi[3];
         tri_box(m, cents[k].id, lo, hi);
         for (int i = 0; i < 3; i++) {
-            n->lo[i] = minf_(n->lo[i], lo[i]);
-            n->hi[i] = maxf_(n->hi[i], hi[i]);
-            clo[i] = minf_(clo[i], cents[k].c[i]);
-            chi[i] = maxf_(chi[i], cents[k].c[i]);
+            /* a NaN bound is ignored, as in the product's builder (fminf / fmaxf): a node box is never NaN, and a triangle
+             * with a NaN bound is hit by no ray (a NaN or infinite coordinate fails the predicate) */
+            n->lo[i] = fminf(n->lo[i], lo[i]);
+            n->hi[i] = fmaxf(n->hi[i], hi[i]);
+            clo[i] = fminf(clo[i], cents[k].c[i]);
+            chi[i] = fmaxf(chi[i], cents[k].c[i]);
         }
     }
     if (count <= 4) {
@@ -433,8 +438,8 @@ void *oracle_mesh_create(const float *verts, int64_t nv, const int32_t *faces, i
         float lo[3], hi[3];
         tri_box(m, (int32_t)f, lo, hi);
         for (int i = 0; i < 3; i++) {
-            mn[i] = minf_(mn[i], lo[i]);
-            mx[i] = maxf_(mx[i], hi[i]);
+            mn[i] = fminf(mn[i], lo[i]); /* (NaN bounds ignored: the product's root box) */
+            mx[i] = fmaxf(mx[i], hi[i]);
         }
     }
     for (int i = 0; i < 3; i++) {

@@ -17,6 +17,12 @@ check_structure raises StructureError (an AssertionError) whose `check` names th
     "height"       the height walked from the root differs from info["depth"] or exceeds 64
     "bounds"       info["aabb_min/max"] is not the union of the padded boxes
     "frame"        the grid frame is not the one derived from those bounds
+
+Meshes with NaN or infinite vertices (tests/hostile_meshes.py) are judged by the same checks: minima and maxima are those
+of fminf / fmaxf (np.fmin / np.fmax: a NaN operand is ignored, two NaN give NaN), reductions start from +Inf / -Inf as the
+builder's do, and floats are compared as bits with EVERY NaN EQUAL TO EVERY NaN (canon_bits): which payload and sign an
+Inf - Inf or a propagated NaN carries differs between an x86 and a gfx950 build and is nobody's contract.  -0 and +0 stay
+different, and so does everything finite.
 """
 import traceback
 
@@ -50,9 +56,10 @@ def _pad(x):
 
 
 def _padded(a, b, c):
-    lo = np.minimum(np.minimum(a, b), c)
-    hi = np.maximum(np.maximum(a, b), c)
-    return np.concatenate([lo - _pad(lo), hi + _pad(hi)], axis=1).astype(F32)
+    lo = np.fmin(np.fmin(a, b), c)
+    hi = np.fmax(np.fmax(a, b), c)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.concatenate([lo - _pad(lo), hi + _pad(hi)], axis=1).astype(F32)
 
 
 def padded_boxes(v, f):
@@ -62,7 +69,8 @@ def padded_boxes(v, f):
 
 def bounds_of(boxes):
     """union of padded boxes: (mn[3], mx[3]) float32"""
-    return boxes[:, :3].min(0).astype(F32), boxes[:, 3:].max(0).astype(F32)
+    return (np.fmin.reduce(boxes[:, :3], axis=0, initial=F32(np.inf)).astype(F32),
+            np.fmax.reduce(boxes[:, 3:], axis=0, initial=F32(-np.inf)).astype(F32))
 
 
 def _spread21(x):
@@ -83,7 +91,7 @@ def morton_keys(v, f):
             c = F32(0.5) * box[:, k] + F32(0.5) * box[:, 3 + k]
             ext = F32(mx[k] - mn[k])
             u = (c - mn[k]) / ext if ext > 0 else np.zeros(len(box), F32)
-            u = np.minimum(np.maximum(u.astype(F32), F32(0)), F32(1))
+            u = np.fmin(np.fmax(u.astype(F32), F32(0)), F32(1))      # fminf(fmaxf(u, 0), 1): a NaN becomes 0
             s = (u * F32(2097152.0)).astype(F32)
             q.append(np.minimum(s.astype(np.int64), 2097151))      # truncation, capped at 2^21 - 1
     return (_spread21(q[0]) << np.uint64(2)) | (_spread21(q[1]) << np.uint64(1)) | _spread21(q[2])
@@ -116,7 +124,27 @@ def record_boxes(tris):
 
 
 def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
+    return canon_bits(np.ascontiguousarray(x, F32))
+
+
+def canon_bits(x):
+    """float32 array (or its uint32 words) -> uint32 words with every NaN replaced by 0x7fc00000"""
+    w = np.ascontiguousarray(x).view(np.uint32).copy()
+    w[(w & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)] = np.uint32(0x7fc00000)
+    return w
+
+
+FLOAT_WORDS = {"nodes": slice(0, 12), "tris": [0, 1, 2, 3, 4, 5, 6, 7, 8, ESUM]}      # (the other words are ids: never touched)
+
+
+def canon_arrays(nodes, links, tris, qnodes, frame):
+    """the five arrays of a hierarchy with the NaNs of their float words made canonical, for byte comparisons"""
+    nodes, tris = np.array(nodes, np.uint32), np.array(tris, np.uint32)
+    if len(nodes):
+        nodes[:, FLOAT_WORDS["nodes"]] = canon_bits(nodes[:, FLOAT_WORDS["nodes"]])
+    if len(tris):
+        tris[:, FLOAT_WORDS["tris"]] = canon_bits(tris[:, FLOAT_WORDS["tris"]])
+    return nodes, links, tris, qnodes, canon_bits(np.asarray(frame, F32)).view(F32)
 
 
 def check_leaf_boxes(nodes, tris):
@@ -128,7 +156,7 @@ def check_leaf_boxes(nodes, tris):
         m = c[:, k] < 0
         slot = ~c[m, k].astype(np.int64)
         _require(np.all((slot >= 0) & (slot < len(tris))), "leaf_boxes", "a leaf id points outside the triangle array")
-        got = nodes[m, 6 * k:6 * k + 6]
+        got = canon_bits(nodes[m, 6 * k:6 * k + 6])
         bad = np.flatnonzero(np.any(got != _bits(want[slot]), axis=1))
         _require(len(bad) == 0, "leaf_boxes", f"{len(bad)} leaf boxes of child {k} differ from the padded triangle box, "
                                               f"first at node {np.flatnonzero(m)[bad[0]] if len(bad) else -1}")
@@ -196,7 +224,8 @@ def check_structure(v, f, nodes, links, tris, qnodes, frame, info, ref_frame=Non
     _require(len(bad) == 0, "order", f"{len(bad)} slots hold another face than the stable sort, first slot "
                                      f"{bad[0] if len(bad) else -1}")
     rec = tri_records(v, f, want_order)
-    bad = np.flatnonzero(np.any(rec != tris, axis=1))
+    rec[:, FLOAT_WORDS["tris"]] = canon_bits(rec[:, FLOAT_WORDS["tris"]])
+    bad = np.flatnonzero(np.any(rec != canon_arrays(np.zeros((0, 16), np.uint32), None, tris, None, np.zeros(6, F32))[2], axis=1))
     _require(len(bad) == 0, "records", f"{len(bad)} triangle records differ, first slot {bad[0] if len(bad) else -1}")
     boxes = padded_boxes(v, f)
     if nf >= 2:

@@ -1,6 +1,6 @@
 // nearest_sim.cpp -- TEST-ONLY: csrc/tr_nearest.h built for the host (libnearest_sim.so, tests/host_sim/nearest_sim.py).
-// Two entries: the brute force of the per-triangle function tr_near_tri over every triangle of a mesh with the
-// lexicographic minimum (d2, face index) -- the oracle of the GPU tests -- and the walk (tr_near_query) over the arrays
+// Two entries: the brute force of the per-triangle function tr_near_tri over every active triangle (tr_near_active: all nine
+// coordinates finite) of a mesh with the lexicographic minimum (d2, face index) -- the oracle of the GPU tests -- and the walk (tr_near_query) over the arrays
 // of a hierarchy (sim.SimBVH: built on the host, or downloaded from the GPU builder), point by point.
 #include <cstdint>
 #include <cstring>
@@ -23,6 +23,7 @@ void sim_nearest_brute(const float* verts, const int32_t* faces, int64_t nf, con
         int32_t bf = -1;
         for (int64_t f = 0; valid && f < nf; f++) {
             const float *a = verts + 3 * faces[3 * f], *b = verts + 3 * faces[3 * f + 1], *c = verts + 3 * faces[3 * f + 2];
+            if (!tr_near_active(a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2])) continue;
             const tr_near_pt q = tr_near_tri(p[0], p[1], p[2], a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]);
             if (bf < 0 || q.d2 < best) { best = q.d2; bp = q; bf = (int32_t)f; }      // (ascending f: the first of equals is the smallest index)
         }

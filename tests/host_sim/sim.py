@@ -98,7 +98,8 @@ class SimBVH:
         base, scale = self.frame[:3], self.frame[3:]
 
         def dec(v, ax):
-            return (v.astype(np.float64) * np.float64(scale[ax]) + np.float64(base[ax])).astype(np.float32)
+            with np.errstate(invalid="ignore", over="ignore"):      # (an infinite frame decodes to NaN: 0 * inf, inf - inf)
+                return (v.astype(np.float64) * np.float64(scale[ax]) + np.float64(base[ax])).astype(np.float32)
         out = np.zeros((len(q), 2, 6), np.float32)
         for k in (0, 1):
             w = q[:, 3 * k:3 * k + 3]

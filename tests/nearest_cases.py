@@ -3,7 +3,8 @@ closest_point checks, an independent numpy float64 point-triangle distance, and 
 
 The numpy side shares no code and no formulation with csrc/tr_nearest.h: the in-plane candidate comes from the 2x2 Gram
 system of (b - a, c - a) and its barycentric coordinates (the core: the normal and three edge functions), everything is
-evaluated for all (point, triangle) pairs at once, nothing is clamped into the triangle's coordinate range."""
+evaluated for all (point, triangle) pairs at once, nothing is clamped into the triangle's coordinate range.  A triangle with
+a NaN or an infinite coordinate is inactive (csrc/tr_nearest.h): its distance from every point is +Inf here."""
 import os
 
 import numpy as np
@@ -90,11 +91,18 @@ def _distance(p, a, b, c):
     return np.where(inside, np.minimum(face, d), d)
 
 
+def active(v, f):
+    """[F] bool: the triangles whose nine coordinates are finite"""
+    return np.isfinite(np.asarray(v, np.float64)[np.asarray(f)]).all(axis=(1, 2))
+
+
 def numpy_distances(v, f, p):
-    """[n, F] float64 distances from every point to every triangle"""
+    """[n, F] float64 distances from every point to every triangle, +Inf to an inactive one"""
     v = np.asarray(v, np.float64)
+    ok = active(v, f)
+    v = np.where(np.isfinite(v), v, 0.0)                  # (placeholders: the columns of inactive triangles are overwritten)
     a, b, c = (v[f[:, k]][None] for k in range(3))
-    return _distance(np.asarray(p, np.float64)[:, None, :], a, b, c)
+    return np.where(ok[None, :], _distance(np.asarray(p, np.float64)[:, None, :], a, b, c), np.inf)
 
 
 def numpy_distances_paired(v, f, tri, p):
@@ -112,7 +120,8 @@ def check_against_numpy(v, f, p, closest, distance, tri, what):
     """the four tolerance checks of the closest_point contract on finite points p; prints each figure before it asserts"""
     v, f, p = np.asarray(v, np.float32), np.asarray(f, np.int32), np.asarray(p, np.float32)
     assert np.isfinite(p).all() and len(f) > 0
-    S = float(max(np.abs(v[f.reshape(-1)]).max(), np.abs(p).max()))
+    assert active(v, f)[tri].all(), f"{what}: an inactive triangle is returned"
+    S = float(max(np.abs(v[f[active(v, f)].reshape(-1)]).max(), np.abs(p).max()))
     eps = 2.0 ** -40 * S
     D = numpy_distances(v, f, p)
     d_min = D.min(1)

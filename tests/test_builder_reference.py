@@ -172,6 +172,51 @@ def test_check_structure_rejects_each_corruption_for_its_own_reason(case):
     assert e.value.check == want and part in str(e.value), str(e.value)
 
 
+# (a leaf box holds a NaN only where all three vertices are NaN, or infinite with one sign, on one axis: the all-NaN triangle)
+HOSTILE_BITE = [(name, seed, case) for name, seed in (("nonfinite", 0), ("faraway_nonfinite", 1), ("deep_nan", 0), ("holed_sphere", None),
+                                                      ("all_nan_triangle", None))
+                for case in ("none", "leaf_box", "internal_box", "nan_for_a_number") + (("nan_payload", "number_for_a_nan") if name == "all_nan_triangle" else ())]
+
+
+@pytest.mark.parametrize("name,seed,case", HOSTILE_BITE)
+def test_check_structure_keeps_its_bite_on_a_hostile_mesh(name, seed, case):
+    """a tree over NaN and infinite vertices (tests/hostile_meshes.py) passes with any NaN payload, and is still rejected
+    when one finite bound is off by one float spacing, when a NaN stands where a number belongs and the other way round"""
+    import hostile_meshes as M
+    m = M.case(name, seed)
+    B = SimBVH(m.v, m.f)
+    mn, mx = K.bounds_of(K.padded_boxes(m.v, m.f))
+    info = dict(depth=B.depth, aabb_min=mn.tolist(), aabb_max=mx.tolist())
+    nodes = B.nodes.copy()
+    c = nodes[:, 12:14].view(np.int32)
+    boxes = nodes[:, :12].view(np.float32)
+    nan = np.isnan(boxes)
+    assert np.isfinite(boxes).any() and (nan.any() or name != "all_nan_triangle") and not np.isfinite(m.v[m.f]).all()
+    leaf = np.repeat(c < 0, 6, axis=1)
+    want = None
+    if case == "nan_payload":
+        nodes[:, :12][nan] = np.uint32(0xffc12345)                                      # another sign, another payload
+    elif case in ("leaf_box", "internal_box"):
+        rows, cols = np.nonzero(np.isfinite(boxes) & (boxes != 0) & (leaf if case == "leaf_box" else ~leaf))
+        r, k = int(rows[len(rows) // 2]), int(cols[len(rows) // 2])
+        nodes[r, k] = _ulp_outward(nodes[r, k], lower=(k % 6) < 3)
+        want = "leaf_boxes" if case == "leaf_box" else "tree: box nesting"
+    elif case == "nan_for_a_number":
+        rows, cols = np.nonzero(np.isfinite(boxes) & leaf)
+        nodes[rows[0], cols[0]] = np.uint32(0x7fc00000)
+        want = "leaf_boxes"
+    elif case == "number_for_a_nan":
+        rows, cols = np.nonzero(nan & leaf)
+        nodes[rows[0], cols[0]] = np.float32(0.5).view(np.uint32)
+        want = "leaf_boxes"
+    if want is None:
+        _check(m.v, m.f, B, info, nodes=nodes)
+        return
+    with pytest.raises(K.StructureError) as e:
+        _check(m.v, m.f, B, info, nodes=nodes)
+    assert e.value.check == want, str(e.value)
+
+
 # ---- node_layout = 0 ----------------------------------------------------------------------------------------------------
 def node_permutation(A, B):
     """p with p[0] = 0 such that node i of tree A is node p[i] of tree B (walked from the root, leaf ids must be equal)"""

@@ -6,6 +6,7 @@ import pytest
 
 import workloads as W
 from oracle.oracle import OracleIntersector
+from bvh_checks import canon_bits
 from sim import SimBVH
 
 Q_ANY, Q_FIRST, Q_CLOSEST, Q_COUNT = 0, 1, 2, 3
@@ -31,27 +32,40 @@ def check_tree(B):
         assert np.array_equal(par[ch[m]], np.flatnonzero(m))
         assert np.array_equal(sib[ch[m]], c[m, 1 - k])
         cb = boxes[ch[m]]
-        lo = np.minimum(cb[:, 0:3], cb[:, 6:9])
-        hi = np.maximum(cb[:, 3:6], cb[:, 9:12])
-        assert np.array_equal(lo, boxes[m, 6 * k:6 * k + 3]) and np.array_equal(hi, boxes[m, 6 * k + 3:6 * k + 6])
+        # (fminf / fmaxf as the builder: a NaN bound of a hostile mesh is ignored; any NaN equals any NaN: bvh_checks.canon_bits)
+        lo = np.fmin(cb[:, 0:3], cb[:, 6:9])
+        hi = np.fmax(cb[:, 3:6], cb[:, 9:12])
+        assert np.array_equal(canon_bits(lo), canon_bits(boxes[m, 6 * k:6 * k + 3])) and np.array_equal(canon_bits(hi), canon_bits(boxes[m, 6 * k + 3:6 * k + 6]))
     faces = B.tris[:, 9].view(np.int32)
     assert np.array_equal(np.sort(faces), np.arange(nf))
     # the 32-byte grid nodes of the unordered schedule: same topology, boxes that CONTAIN the exact
     # child boxes (bit-exact decode), nest, and are tight to one grid cell where float spacing allows
     assert np.array_equal(B.qnodes[:, 6:8].view(np.int32), c)
+    # An axis whose frame is not finite (a mesh with infinite vertices or padded boxes that overflow) is ignored by the
+    # fused box test (tr_fuse_axis: M beyond 1e30 or not finite) and judged by nothing here; on a usable axis a bound that is
+    # NaN (a triangle whose three vertices are NaN on it) cannot be contained and is no ray's business, and an infinite one
+    # is held to containment only (`usable` and `known` are all true for a finite mesh).
     qb = B.qchild_boxes()
     scale = B.frame[3:]
+    with np.errstate(invalid="ignore", over="ignore"):
+        usable = np.isfinite(B.frame[:3]) & np.isfinite(B.frame[:3] + np.float32(65535.0) * scale)
     for k in (0, 1):
         ex_lo = boxes[:, 6 * k:6 * k + 3]                           # stored lo.x lo.y lo.z | hi.z hi.x hi.y
         ex_hi = boxes[:, [6 * k + 4, 6 * k + 5, 6 * k + 3]]
-        assert np.all(qb[:, k, :3] <= ex_lo) and np.all(qb[:, k, 3:] >= ex_hi)
-        slack = np.maximum(scale, np.spacing(np.maximum(np.abs(ex_lo), np.abs(ex_hi)).astype(np.float32)) * 2)
-        assert np.all(ex_lo - qb[:, k, :3] <= slack * 1.0001) and np.all(qb[:, k, 3:] - ex_hi <= slack * 1.0001)
+        known_lo, known_hi = usable & ~np.isnan(ex_lo), usable & ~np.isnan(ex_hi)
+        assert np.all((qb[:, k, :3] <= ex_lo) | ~known_lo) and np.all((qb[:, k, 3:] >= ex_hi) | ~known_hi)
+        tight_lo, tight_hi = known_lo & np.isfinite(ex_lo), known_hi & np.isfinite(ex_hi)
+        with np.errstate(invalid="ignore"):
+            slack = np.maximum(scale, np.spacing(np.fmax(np.abs(ex_lo), np.abs(ex_hi)).astype(np.float32)) * 2)
+            assert np.all((ex_lo - qb[:, k, :3] <= slack * 1.0001) | ~tight_lo) and np.all((qb[:, k, 3:] - ex_hi <= slack * 1.0001) | ~tight_hi)
         ch = c[:, k]
         m = ch >= 0
-        cb = qb[ch[m]]
-        assert np.all(qb[m, k, :3] <= np.minimum(cb[:, 0, :3], cb[:, 1, :3]))
-        assert np.all(qb[m, k, 3:] >= np.maximum(cb[:, 0, 3:], cb[:, 1, 3:]))
+        cb, ce = qb[ch[m]], boxes[ch[m]]
+        # (a NaN bound becomes plane 0 / 65535, tr_qfloor / tr_qceil, which the parent, whose exact box ignores it, need not contain)
+        cb_lo = np.minimum(np.where(np.isnan(ce[:, 0:3]), np.inf, cb[:, 0, :3]), np.where(np.isnan(ce[:, 6:9]), np.inf, cb[:, 1, :3]))
+        cb_hi = np.maximum(np.where(np.isnan(ce[:, [4, 5, 3]]), -np.inf, cb[:, 0, 3:]), np.where(np.isnan(ce[:, [10, 11, 9]]), -np.inf, cb[:, 1, 3:]))
+        assert np.all((qb[m, k, :3] <= cb_lo) | ~usable)
+        assert np.all((qb[m, k, 3:] >= cb_hi) | ~usable)
 
 
 def compare_all(v, f, o, d, **kw):

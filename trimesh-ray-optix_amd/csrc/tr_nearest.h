@@ -25,7 +25,13 @@
 //  * Outputs: closest = the winning triangle's candidate point, each float64 component rounded to float32 (it stays
 //    inside the triangle's coordinate range: the clamp); distance = (float)sqrt(d2), the square root in float64, +Inf
 //    where it exceeds the float range (tr_near_distance); tri = the original face index.
-//  * A point with a non-finite component, or a mesh of zero triangles: tri = -1, distance = +Inf, closest = NaN.
+//  * INACTIVE TRIANGLES.  A triangle with a NaN or an infinite coordinate (tr_near_active is false) offers no candidate: it
+//    is not part of "the set of triangles" above, exactly as no ray hits it (arithmetic contract, "Meshes").
+//    Without this a triangle with ONE infinite vertex still has finite edges and wins with a finite distance.  The
+//    hierarchy keeps such triangles as leaves; their boxes may hold NaN or Inf, which the bound below turns into 0 or into
+//    a bound that no finite best exceeds wrongly (a NaN difference selects 0, the smallest bound there is).
+//  * A point with a non-finite component, a mesh of zero triangles, or a mesh whose triangles are all inactive: tri = -1,
+//    distance = +Inf, closest = NaN.
 //
 // THE BOUND (culling).  A subtree is skipped only when tr_near_box(p, its box) > best d2 so far, STRICTLY: a tie is
 // never culled.  tr_near_box is, per axis, g_k = max(fl(lo_k - p_k), fl(p_k - hi_k), 0) in float64, and
@@ -143,12 +149,20 @@ TR_HD float tr_near_distance(double d2) {
 TR_HD void tr_near_init(tr_near_best& best) { best.d2 = INFINITY; best.face = 0x7fffffff; best.slot = -1; }
 TR_HD bool tr_near_lost(uint32_t sp) { return (sp & 1u) != 0; }
 
-// one triangle against the best so far: (d2, face) lexicographic
+// all nine coordinates finite (see INACTIVE TRIANGLES)
+TR_HD bool tr_near_active(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz) {
+    return tr_finite(ax) && tr_finite(ay) && tr_finite(az) && tr_finite(bx) && tr_finite(by) && tr_finite(bz) && tr_finite(cx) &&
+           tr_finite(cy) && tr_finite(cz);
+}
+
+// one triangle against the best so far: (d2, face) lexicographic; an inactive triangle changes nothing (a select, not a
+// branch: the arithmetic on its NaN / Inf is harmless and the control flow stays that of the finite case)
 TR_HD void tr_near_leaf(const tr_bvh_view& b, int32_t slot, float px, float py, float pz, tr_near_best& best) {
     tr_counters* nc = nullptr;
     const tr_tri t = tr_load_tri<false, false>(b, slot, nc);
     const tr_near_pt c = tr_near_tri(px, py, pz, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz);
-    if (c.d2 < best.d2 || (c.d2 == best.d2 && t.face < best.face)) { best.d2 = c.d2; best.face = t.face; best.slot = slot; }
+    const bool active = tr_near_active(t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz);
+    if (active && (c.d2 < best.d2 || (c.d2 == best.d2 && t.face < best.face))) { best.d2 = c.d2; best.face = t.face; best.slot = slot; }
 }
 
 // both child boxes and child ids of an internal node
@@ -213,7 +227,7 @@ TR_HD void tr_near_visit(const tr_bvh_view& b, float px, float py, float pz, tr_
 
 // The seed descent, one node per call: from `node` to its nearer child, without a stack and without culling, down to one
 // leaf, which is evaluated.  Returns the next node, -1 after the leaf.  It gives the walk a finite best before its first
-// push: without it the first descent of the walk culls nothing and pushes a far child at EVERY level -- a stack as deep as
+// push (unless that leaf is inactive: the walk then starts as if there were no seed, correct and only slower): without it the first descent of the walk culls nothing and pushes a far child at EVERY level -- a stack as deep as
 // the hierarchy.  Measured on the host (20 000 hash points in 1.2x the box of an 81 920-triangle displaced icosphere, 23
 // levels): without the seed 68 % of the walks need more than 16 entries, with it 6 %; the median need is 11-12 entries, the
 // largest 21 -- points deep inside a near-sphere are nearly equidistant from much of the surface and keep a far child

@@ -288,7 +288,8 @@ class RayMeshIntersector:
         """trimesh.proximity.closest_point: (closest[*b,3] float32, distance[*b] float32, triangle_id[*b] int32) of
         points [*b, 3], one launch of libtriro_nearest.so (tr_closest_point).  Distances are evaluated in float64 from
         the float32 inputs; among triangles at exactly the same distance the smaller face index wins (trimesh leaves
-        that open).  A point with a non-finite component, or an empty mesh: (NaN, +Inf, -1).  Points are converted to
+        that open).  A triangle with a NaN or an infinite coordinate is inactive: never returned, as no ray hits it.  A point
+        with a non-finite component, an empty mesh or one without an active triangle: (NaN, +Inf, -1).  Points are converted to
         contiguous float32 on the acceleration structure's GPU; a tensor on another GPU raises."""
         dev = self.mesh_vertices.device
         if isinstance(points, torch.Tensor):
