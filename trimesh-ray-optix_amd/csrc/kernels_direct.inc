@@ -62,15 +62,19 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                                                     tr_result& res, tr_counters* cnt,
                                                     const tr_ring ring, int32_t* wl, int lane,
                                                     uint32_t steal_min, bool& lost) {
-    // the grid-node launch walks with the plain far-child stack (tr_plain_w, tr_bvh.h: no trail words, so DEEP is the same
-    // code); the launch on the exact nodes (option grid_nodes = 0) keeps the dense stack and never loses a child
+    // the grid-node launch walks with the plain far-child stack, its stack pointer an LDS byte address (tr_plaina_w,
+    // tr_bvh.h: no trail words, so DEEP is the same code); the launch on the exact nodes (option grid_nodes = 0) keeps the
+    // dense stack and never loses a child
     constexpr bool PLAIN = QN;
-    typedef typename std::conditional<PLAIN, tr_plain_w, typename tr_word<COMPACT, DEEP>::T>::type W;
+    typedef typename std::conditional<PLAIN, tr_plaina_w, typename tr_word<COMPACT, DEEP>::T>::type W;
     lost = false;
     tr_result_init(res);
     tr_topk<1> top;
     tr_state_t<W> fs;
-    tr_state_init(fs);
+    const tr_aring ar = tr_aring_of(ring);
+    (void)ar;
+    if constexpr (PLAIN) tr_state_init(fs, tr_addr_start(ring));
+    else tr_state_init(fs);
     if (!go) fs.node = -1;
     auto trip_step = [&](auto test_tag) {
         constexpr bool TEST = decltype(test_tag)::value;
@@ -108,7 +112,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     lds_i32* const list = lw;                    // [64] donor lane of pair k
     lds_i32* const xnode = lw + 64;              // [64] node handed over by donor lane
     // [64] dense stack: the depth of the node handed over.  Plain stack: per lane, bits 0-7 = entries this lane has given
-    // away since its stack was last empty (`bot`, tr_plain_give), bit 8 = a lane that worked on THIS lane's ray lost a
+    // away since its stack was last empty (`bot`, tr_addr_give), bit 8 = a lane that worked on THIS lane's ray lost a
     // far child (set by that lane when it hands its results in)
     lds_i32* const xdepth = lw + 128;
     int32_t* const xflags = wl + 128;
@@ -123,7 +127,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     lds_i32* const vslots = lw + ACC + 128;
     auto deposit = [&]() {
         if constexpr (PLAIN) {
-            if (tr_plain_lost(fs.sp)) atomicOr(&xflags[owner], 0x100);
+            if (tr_addr_lost(fs.sa)) atomicOr(&xflags[owner], 0x100);
         }
         if (Q == TR_Q_COUNT) {
             if (res.count) atomicAdd(&sum[owner], res.count);
@@ -190,7 +194,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             bool has_far;                            // owed far children that are in the stack
             if constexpr (PLAIN) {
                 bot = (uint32_t)xdepth[lane] & 0xffu;
-                has_far = tr_plain_can_give(fs.sp, bot);
+                has_far = tr_addr_can_give(ar, fs.sa, bot);
             } else {
                 has_far = (fs.trail & fs.owned) != 0;
             }
@@ -211,8 +215,8 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                 (void)gdepth;
                 if constexpr (PLAIN) {
                     if (give) {
-                        // the shallowest = the bottom of the stack; -1 takes its place (tr_plain_give)
-                        gnode = tr_plain_give(ring, bot);
+                        // the shallowest = the bottom of the stack; -1 takes its place (tr_addr_give)
+                        gnode = tr_addr_give(ar, fs.sa, bot);
                         list[drank] = lane; xnode[lane] = gnode;
                         atomicAdd(&xflags[lane], 1);
                     }
@@ -248,10 +252,14 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                 const float bt = __shfl(res.best_t, src);
                 if (take) {
                     owner = own2;
-                    tr_state_init(fs);
+                    if constexpr (PLAIN) {
+                        tr_state_init(fs, tr_addr_bottom(ar, fs.sa));      // an empty stack again: the lane's slot 0 ...
+                        atomicAnd(&xflags[lane], 0x100);                   // ... and nothing given away
+                    } else {
+                        tr_state_init(fs);
+                        fs.depth = (uint32_t)xdepth[src];
+                    }
                     fs.node = xnode[src];
-                    if constexpr (PLAIN) atomicAnd(&xflags[lane], 0x100);      // an empty stack: nothing given away
-                    else fs.depth = (uint32_t)xdepth[src];
                     tr_set_best_t(res, bt);
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -277,7 +285,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
         }
         if constexpr (PLAIN) lost = (xdepth[lane] & 0x100) != 0;
     } else if constexpr (PLAIN) {
-        lost = tr_plain_lost(fs.sp);
+        lost = tr_addr_lost(fs.sa);
     }
     return split;
 }
@@ -313,7 +321,7 @@ __device__ __forceinline__ void process_ray(const tr_bvh_view& b, const RayFetch
     if (in_range) write_result<Q>(b, out, i, r, res);
 }
 
-// The rays of a wave whose plain far-child stack lost a child (tr_plain_push; on the lane that owns the ray or on a thief):
+// The rays of a wave whose plain far-child stack lost a child (tr_addr_push; on the lane that owns the ray or on a thief):
 // traversed once more, from the best hit so far, by the stackless walk over the exact nodes (tr_traverse_more).  A real call
 // behind a branch marked as unlikely, like the float64 part of the hit predicate (tr_drain_exact<COLD>): what it needs is
 // saved around the call and it puts nothing into the trips.  Everything arrives by value -- a pointer to the caller's view or
@@ -689,7 +697,7 @@ __device__ __forceinline__ void query_direct_body(const tr_bvh_view& b, const Ra
     int64_t nblk = gridDim.x - slot_shift;
     const unsigned long long t_start = cost ? wall_clock64() : 0ull;
     __shared__ int32_t ring_lds[MODE == 4 ? 1 : TR_RING * BS];
-    const tr_ring ring = {ring_lds + threadIdx.x, BS};
+    const tr_ring ring = {ring_lds + threadIdx.x, BS, ring_lds};
     constexpr int SCR = 384;          // ints of stealing scratch per wave (MODE 1)
     __shared__ alignas(8) int32_t steal_lds[MODE == 1 ? (BS / 64) * SCR : (JOB ? 16 : 2)];
     if constexpr (JOB) {

@@ -455,6 +455,7 @@ TR_HD bool tr_drain_exact(const tr_bvh_view& b, const tr_ray& r, int32_t& pe, tr
 struct tr_ring {
     int32_t* base;   // nullptr = no stack (always climb)
     int32_t stride;
+    int32_t* row0;   // slot 0 of the block's FIRST lane (the address form of the plain stack, tr_aring); nullptr = base
 };
 // Ring accesses go through an explicit LDS pointer on the device.  With the generic pointer the compiler
 // merged "pop the ring slot (LDS)" and "read the sibling from links[] (global)" -- two 4-byte loads that
@@ -588,6 +589,87 @@ TR_HD bool tr_plain_can_give(uint32_t sp, uint32_t bot) { return (sp >> 1) > bot
 TR_HD int32_t tr_plain_give(const tr_ring ring, uint32_t& bot) {
     const int32_t node = tr_ring_get(ring, bot);
     tr_ring_put(ring, bot, -1);
+    bot++;
+    return node;
+}
+
+// ---- the plain stack by LDS byte address (round 10): what the kernels run -------------------------------------------
+// The same stack, the same slots, the same hand-over; what the lane keeps is not a slot count but
+//   sa = the BYTE ADDRESS of its next free slot, counted from slot 0 of the block's first lane (tr_ring::row0: a
+//   constant of the kernel that the LDS instructions carry in their offset field; on the host an int32_t[]),
+// so that a push is a store and an add and a pop a subtraction and a load: no shift, no merge with the lane's base.  Slot
+// s of lane t lies at 4 * t + s * stride with stride = 4 * block size > 4 * t, so WHICH slot an address belongs to does
+// not depend on the lane and both ends of the stack are compile-time constants:
+//   push: sa < TR_RING * stride (UNSIGNED) ? store at sa, sa += stride : the child is lost;
+//   pop:  sa < stride (SIGNED) ? nothing left (-1) : sa -= stride, load at sa.
+// The sticky `lost` flag is bit 31 of sa, set by the push that does not fit.  It costs the trips nothing and no access
+// ever uses an address with the flag in it: to the push's unsigned test a flagged sa is beyond the top (every later
+// child is dropped as well), to the pop's signed test it is below the bottom -- the walk goes on down to the next node
+// without a hit child and ENDS at that pop.  The ray is traversed again from the top anyway (tr_traverse_more), so
+// nothing the walk would still find is needed.  The form above (sp) goes on walking after a loss; up to the loss the
+// two hand out the same nodes (tests/host_sim/plain_addr_model.cpp drives them side by side).
+struct tr_plaina_w {};     // selects this walk in tr_fused_body
+template <>
+struct tr_state_t<tr_plaina_w> {
+    int32_t node;     // next internal node to visit, -1 = nothing left
+    uint32_t sa;      // byte address of the next free slot | lost
+    int32_t p0, p1, p2;
+    int32_t pe;
+};
+typedef tr_state_t<tr_plaina_w> tr_astate;
+struct tr_aring {
+    int32_t* row0;    // address 0: slot 0 of the block's first lane
+    uint32_t stride;  // bytes from one slot of a lane to its next
+};
+TR_HD tr_aring tr_aring_of(const tr_ring& ring) { return tr_aring{ring.row0 ? ring.row0 : ring.base, 4u * (uint32_t)ring.stride}; }
+// a fresh walk's sa: the lane's slot 0
+TR_HD uint32_t tr_addr_start(const tr_ring& ring) { return ring.row0 ? 4u * (uint32_t)(ring.base - ring.row0) : 0u; }
+TR_HD void tr_state_init(tr_astate& st, uint32_t sa0) {
+    st.node = 0; st.sa = sa0;
+    st.p0 = -1; st.p1 = -1; st.p2 = -1; st.pe = -1;
+}
+TR_HD int32_t tr_addr_get(const tr_aring& ar, uint32_t addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) int32_t tr_lds_i32;
+    typedef __attribute__((address_space(3))) char tr_lds_i8;
+    return *(tr_lds_i32*)((tr_lds_i8*)ar.row0 + addr);
+#else
+    return ar.row0[addr >> 2];
+#endif
+}
+TR_HD void tr_addr_put(const tr_aring& ar, uint32_t addr, int32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) int32_t tr_lds_i32;
+    typedef __attribute__((address_space(3))) char tr_lds_i8;
+    *(tr_lds_i32*)((tr_lds_i8*)ar.row0 + addr) = v;
+#else
+    ar.row0[addr >> 2] = v;
+#endif
+}
+constexpr uint32_t TR_ADDR_LOST = 0x80000000u;
+TR_HD void tr_addr_push(const tr_aring& ar, uint32_t& sa, int32_t node) {
+    if (sa < TR_RING * ar.stride) {
+        tr_addr_put(ar, sa, node);
+        sa += ar.stride;
+    } else {
+        sa |= TR_ADDR_LOST;
+    }
+}
+TR_HD int32_t tr_addr_pop(const tr_aring& ar, uint32_t& sa) {
+    if ((int32_t)sa < (int32_t)ar.stride) return -1;
+    sa -= ar.stride;
+    return tr_addr_get(ar, sa);
+}
+TR_HD bool tr_addr_lost(uint32_t sa) { return (sa & TR_ADDR_LOST) != 0; }
+// Outside the trips (the hand-over of wave_traverse_steal): the lane's slot 0 and its slots in use, from sa alone
+TR_HD uint32_t tr_addr_bottom(const tr_aring& ar, uint32_t sa) { return (sa & ~TR_ADDR_LOST) % ar.stride; }
+TR_HD uint32_t tr_addr_slots(const tr_aring& ar, uint32_t sa) { return (sa & ~TR_ADDR_LOST) / ar.stride; }
+// (a walk that lost a child gives nothing more away: it ends at its next pop)
+TR_HD bool tr_addr_can_give(const tr_aring& ar, uint32_t sa, uint32_t bot) { return !tr_addr_lost(sa) && tr_addr_slots(ar, sa) > bot; }
+TR_HD int32_t tr_addr_give(const tr_aring& ar, uint32_t sa, uint32_t& bot) {
+    const uint32_t a = tr_addr_bottom(ar, sa) + bot * ar.stride;
+    const int32_t node = tr_addr_get(ar, a);
+    tr_addr_put(ar, a, -1);
     bot++;
     return node;
 }
@@ -889,6 +971,16 @@ TR_HD void tr_fused_body(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
             st.node = swap ? c1 : c0;
             if (!(h0 || h1)) st.node = tr_plain_pop(ring, st.sp);
         }
+    } else if constexpr (std::is_same<W, tr_plaina_w>::value) {
+        // the same walk with the stack pointer as an LDS byte address (tr_addr_push), in the same order
+        if (go) {
+            const tr_aring ar = tr_aring_of(ring);
+            const bool both = h0 && h1;
+            const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
+            if (both) tr_addr_push(ar, st.sa, swap ? c0 : c1);
+            st.node = swap ? c1 : c0;
+            if (!(h0 || h1)) st.node = tr_addr_pop(ar, st.sa);
+        }
     } else if (go) {
         if (h0 || h1) {
             const bool both = h0 && h1;
@@ -980,8 +1072,9 @@ TR_HD void tr_fused_step(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
         }
     }
 #endif
-    // node index or 0, from the sign bits (a select here loses the SGPR-base + 32-bit-offset
-    // addressing of the four node loads)
+    // node index or 0, from the sign bits.  (A select under `has_node` keeps the SGPR-base + 32-bit-offset form of the
+    // node loads with the present compiler -- the loss of it was the reason for this form -- and is two VALU instructions
+    // shorter in the loop of two trips, but measured no faster: DESIGN_experiments.md part R10.)
     const int32_t nidx = st.node & ~(st.node >> 31) & (room >> 31);
     if constexpr (QN) {
         const tr_i4* np = tr_qnode_ptr<COMPACT>(b, nidx);
@@ -1117,7 +1210,7 @@ TR_HD void tr_traverse_unordered(const tr_bvh_view& b, const tr_ray& r, bool val
     }
 }
 
-// The second traversal of a ray whose plain stack lost a far child (tr_plain_push): the whole hierarchy once more with
+// The second traversal of a ray whose plain stack lost a far child (tr_plain_push / tr_addr_push): the whole hierarchy once more with
 // the stackless walk over the exact nodes (no ring: every far child is found by climbing), `res` keeping what the first
 // traversal found -- its best hit is the starting bound (closest / first), a hit ends it at once (any).  `r` needs the
 // constants of tr_ray_setup_a only.
