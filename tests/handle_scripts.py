@@ -216,7 +216,7 @@ TILED = {"tile": 2, "split": 2}          # 8 x 8 tiles and split blocks at 128 b
 
 def _pending_meets_rebuild():
     """1.  Under TILED the first launch of a shape runs plain, the second takes the wanted shape and resets `launches`, so
-    it is the FIFTH launch that measures in the steady state and defers its sort (launches == 3 in sched_acquire), and the
+    it is the FIFTH launch that measures in the steady state and defers its sort (launches == 3 in sched_measure), and the
     sixth that carries it and flips `cur`.  (The issue counted the fourth and the fifth: that holds where the plain and the
     wanted shape are the same, as in scripts 2 and 7.)  The mesh changes once while the sort is pending and once right
     after it was carried; afterwards the waiting sort cannot ride in a launch that measures and runs as a kernel of its own."""
@@ -235,7 +235,7 @@ def _pending_meets_rebuild():
 
 def _pending_meets_option_flips():
     """2.  Default options: the plain and the wanted shape are one, so the fourth launch of the shape (launches == 3 in
-    sched_acquire, and every fourth after it) measures and defers its sort.  Each flip meets such a waiting sort: the option
+    sched_measure, and every fourth after it) measures and defers its sort.  Each flip meets such a waiting sort: the option
     changes for its launches, goes back, and default launches run on to the next deferred sort (`launches` is in the
     comments).  sort_inline = 0, grid_nodes = 0, compact = 0 and steal = 0 cannot carry it -- it runs as a kernel of its own
     in front --, adaptive = 0 leaves the slot alone and the sort waiting (the first launch under adaptive = 1 carries it),

@@ -6,7 +6,7 @@ for output elements that were never written; every script asserts through tr_bvh
 is about: a learned order, split blocks, a carried sort, addressing 2, launch shape 4.  The launch count and the wall time
 of each script are printed, not asserted (DESIGN.md has the figures of an MI355X).
 
-Expectations corrected against the first reading of csrc/launch_policy.inc: under tile = 2, split = 2 the plain and the
+Expectations corrected against the first reading of csrc/launch_policy.inc (sched_first_launches, sched_measure): under tile = 2, split = 2 the plain and the
 wanted launch shape differ, the second launch of a batch shape starts `launches` again, and so the FIFTH launch of a shape
 defers its sort and the sixth carries it (script 1 runs 5 and 6 launches before its transitions, not 4 and 5); with default
 options the two shapes are one and the fourth launch defers (scripts 2, 6 and 7).  A refit, unlike update_raw, leaves

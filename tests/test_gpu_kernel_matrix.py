@@ -1,9 +1,11 @@
 """Every traversal kernel flavour, every multi-hit cap and the scan / compaction edges against exact references.
 
-test_flavour_matches_the_oracle crosses the five queries with the three addressing flavours of launch_query
-(csrc/launch_policy.inc: compact = 32-bit offsets and trail, deep = 32-bit offsets and a 64-bit trail for hierarchies
-of more than 32 levels, generic = 64-bit, forced on small meshes by compact = 0) and the launch shapes the live
-options select.  A combination that launch_policy.inc cannot produce is skipped with the line that rules it out.
+test_flavour_matches_the_oracle crosses the five queries with the three addressing flavours of a query launch
+(csrc/launch_policy.inc, `addr32` / `compact` / `deep` of launch_query: compact = 32-bit offsets and trail, deep = 32-bit
+offsets and a 64-bit trail for hierarchies of more than 32 levels, generic = 64-bit, forced on small meshes by
+compact = 0) and the launch shapes the live
+options select.  A combination that launch_policy.inc cannot produce is skipped with the function (and variable) of that
+file that rules it out.
 Each case compares every output with the oracle bit for bit and, for a direct launch, checks that tr_bvh_last_launch
 reports the (query, shape, node flavour, addressing, sort carried) the case claims.  Streaming launches leave no
 record: their flavour follows from the options (stream = 2 always streams) and the hierarchy's depth, which the
@@ -91,24 +93,24 @@ def check_query(q, got, exp, what):
 # launch shape -> (options, applicable queries, addressing flavours, why the others do not exist)
 SHAPES = {
     "plain": (dict(stream=0, steal=0, wide_direct=0), PRUNING, ("compact", "deep", "generic"),
-              "launch_policy.inc:680: the plain shape exists for the pruning queries only"),
+              "launch_direct (unord): the plain shape, its last else, exists for the pruning queries only"),
     "steal_exact": (dict(stream=0, steal=2, grid_nodes=0, wide_direct=0), PRUNING, ("compact", "deep", "generic"),
-                    "launch_policy.inc:350: stealing (steal) exists for the pruning queries only"),
+                    "decide_direct_shape (steal): stealing exists for the pruning queries only"),
     "steal_grid": (dict(stream=0, steal=2, grid_nodes=1, sort_inline=0, wide_direct=0), PRUNING, ("compact", "deep"),
-                   "launch_policy.inc:570: grid nodes in stealing launches of the pruning queries with 32-bit offsets only"),
+                   "launch_direct (qn_used): grid nodes in stealing launches of the pruning queries with 32-bit offsets only"),
     "sort_carried": (dict(stream=0, steal=2, grid_nodes=1, usteal=1, sort_inline=1, wide_direct=0), PRUNING + ("count",),
                      ("compact", "deep"),
-                     "launch_policy.inc:547: the sort rides in stealing grid-node / stealing count launches with 32-bit offsets only"),
+                     "launch_direct (can_carry): the sort rides in stealing grid-node / stealing count launches with 32-bit offsets only"),
     "unord": (dict(stream=0, usteal=0, wide_direct=0), ("count", "location"), ("compact", "deep", "generic"),
-                  "launch_policy.inc:532: the unordered schedule is the one of count and location"),
+                  "launch_direct (unord): the unordered schedule is the one of count and location"),
     "usteal": (dict(stream=0, usteal=1, sort_inline=0, wide_direct=0), ("count",), ("compact", "deep", "generic"),
-               "launch_policy.inc:353: hand-over between lanes of the unordered schedule exists for count only"),
+               "decide_direct_shape (usteal): hand-over between lanes of the unordered schedule exists for count only"),
     "stream": (dict(stream=2, wide=0), PRUNING + ("count",), ("compact", "deep", "generic"),
-               "launch_policy.inc:520: the location query has no streaming launch"),
+               "decide_streaming: the location query has no streaming launch"),
     "stream_wide": (dict(stream=2, wide=1), PRUNING + ("count",), ("compact", "deep"),
-                    "launch_policy.inc:520 / :441: no streaming location launch; 8-wide nodes with 32-bit offsets only"),
+                    "decide_streaming / launch_streaming (wn): no streaming location launch; 8-wide nodes with 32-bit offsets only"),
     "wide_direct": (dict(stream=0, wide_direct=3), QUERIES, ("compact", "deep"),
-                    "launch_policy.inc:360: the direct launch on 8-wide nodes exists with 32-bit offsets only"),
+                    "decide_direct_shape (use_wd): the direct launch on 8-wide nodes exists with 32-bit offsets only"),
 }
 # tr_launch_info.shape of each direct shape: 0 plain, 1 stealing, 2 unordered, 3 unordered with hand-over, 4 8-wide
 SHAPE_ID = {"plain": 0, "steal_exact": 1, "steal_grid": 1, "unord": 2, "usteal": 3, "wide_direct": 4}

@@ -76,7 +76,7 @@ def test_image_with_every_wave_handing_over(device, query, deep):
 
 @pytest.mark.parametrize("query", PRUNING)
 def test_launch_that_carries_the_sort(device, query):
-    """128 x 128 pixels: an order is learned from 64 blocks on (launch_policy.inc), and its sort rides in a later launch"""
+    """128 x 128 pixels: an order is learned from 64 blocks on (launch_policy.inc, sched_acquire), and its sort rides in a later launch"""
     from triro.ray.ray_optix import RayMeshIntersector
     v, f, o, d, exp = _image(False, 128)
     with options(stream=0, steal=2, grid_nodes=1, sort_inline=1, wide_direct=0):

@@ -96,7 +96,7 @@ def test_small_image_launched_six_times(device, query):
 
 @pytest.mark.parametrize("query", PRUNING)
 def test_image_tiles_split_blocks_and_the_learned_order(device, query):
-    """The default policy gives an image of 32 blocks neither tiles nor a learned order (launch_policy.inc: an order is
+    """The default policy gives an image of 32 blocks neither tiles nor a learned order (launch_policy.inc, sched_acquire: an order is
     learned from 64 blocks on, tiles and split blocks come with much larger launches).  128 x 128 pixels = 128 blocks with
     8 x 8 tiles and split blocks switched on by option reach all of it: the cold launch, the measuring launches, the
     learned order with split blocks (lanes that start idle and steal at once) and the launch that carries the sort."""

@@ -140,7 +140,7 @@ int tr_device_topology(int device, tr_topology* out) {
     out->resident_lanes = (int64_t)st->num_cus * st->waves_per_cu * 64;
     out->steal_max_rays = tr_policy::steal_max_rays(st);
     out->wide_min_rays = tr_policy::wide_min_rays(st);
-    out->count_stream_min_rays = tr_policy::stream_min_rays(st, TR_Q_COUNT, 0);
+    out->count_stream_min_rays = tr_policy::stream_min_rays(st, TR_Q_COUNT);
     return TR_OK;
 }
 

@@ -34,6 +34,10 @@ int tr_fail(int code, const std::string& msg);
 // (launch_policy.inc)
 constexpr int TR_SCHED_MAX = 131072;  // blocks (x256 rays) up to which the order is learned
 constexpr int TR_SCHED_SLOTS = 16;   // (stream, class) pairs per handle: 8 streams x {plain, split} orders
+// what k_sched_sort is told about the launch whose block costs it sorts: its blocks and the chunk size of its XCD map; the split
+// blocks per XCD (two launch slots each, the first split4 of them four); a block is split only from outlier8 / 8 of the mean
+// cost and floor_ticks of the device clock on
+struct tr_sort_params { int nblocks = 0, xc = 0, split = 0, split4 = 0, outlier8 = 0, floor_ticks = 0; };
 struct tr_sched_slot {
     hipStream_t stream = nullptr;
     int cls = 0;            // 1: orders with split blocks (launch shapes that steal), 0: plain
@@ -50,10 +54,10 @@ struct tr_sched_slot {
     // Two order buffers: launches read order_buf(cur) while a sort writes the other one.  A sort that was DEFERRED
     // (`pending`: the costs of the last measuring launch are still unsorted) rides in the next launch of the same shape
     // as an extra workgroup (tr_sort_job, query_direct_body) or, if that launch cannot carry it, runs as k_sched_sort
-    // before it; p_* = what that sort needs.
+    // before it; pending_sort = what that sort needs.
     int cur = 0;
     bool pending = false;
-    int p_nblocks = 0, p_xc = 0, p_split = 0, p_split4 = 0, p_outlier8 = 0, p_floor = 0;
+    tr_sort_params pending_sort;
     // per-lane stack overflow rows of the wide streaming launch on this stream (k_query_wide; grown on demand)
     int32_t* wspill = nullptr;
     size_t wspill_elems = 0;
