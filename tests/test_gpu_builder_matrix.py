@@ -375,3 +375,25 @@ def test_bad_face_beyond_the_grid_cap(device):
     got, info = download(r), r.bvh_info()
     K.check_structure(v, f, *got, info)
     assert_answers(r, v, f, device, "rebuilt after a failed refit", n=1000)
+
+
+def test_load_that_fails_after_the_arena_exists(device):
+    """a blob whose header claims 256 arena bytes fewer than 80 triangles use (the buffer is as long as it was) passes the
+    header checks and is refused once the new handle owns an arena on the device: the one load failure that has device
+    memory to give back.  The library loads the untouched blob afterwards as if nothing had happened."""
+    from triro.ray.ray_optix import OptixAccelStructureWrapper
+    v, f = W.icosphere(1)
+    r = make(v, f, device)
+    built = download(r)
+    blob = r.as_wrapper.serialize()
+    bad = blob.copy()
+    arena_bytes = bad[24:32].view(np.int64)      # magic[8] | num_tris | num_nodes | arena_bytes
+    assert arena_bytes[0] == len(blob) - 80
+    arena_bytes[0] -= 256
+    w = OptixAccelStructureWrapper()
+    with pytest.raises(ValueError, match="arena size mismatch"):
+        w.deserialize(bad, device)
+    fresh = OptixAccelStructureWrapper()
+    fresh.deserialize(blob, device)
+    loaded = fresh.download() + fresh.download_qnodes()
+    assert_same_arrays(loaded, built, "loaded after a failed load")

@@ -105,7 +105,7 @@ int tr_get_device_state(int device, tr_device_state** out) {
             return tr_fail(TR_ERR_NO_DEVICE, "no HIP device available (libtriro_hip has no CPU fallback)");
         if (device >= count) return tr_fail(TR_ERR_NO_DEVICE, "device ordinal >= device count");
         tr_device_guard g;
-        if (g.enter(device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+        TR_TRY(tr_enter_device(&g, device));
         hipDeviceProp_t prop;
         TR_HIP_TRY(hipGetDeviceProperties(&prop, device));
         st.device = device;
@@ -156,6 +156,24 @@ int tr_build_temp_release(tr_device_state* st) {
     return status;
 }
 
+// a fresh handle on `device`, with nothing on the device yet; NULL if the host is out of memory
+static tr_bvh* handle_new(int device) {
+    tr_bvh* bvh = new (std::nothrow) tr_bvh();
+    if (!bvh) return nullptr;
+    bvh->device = device;
+    bvh->sched_mutex = new (std::nothrow) std::mutex();
+    return bvh;
+}
+
+// Gives up a handle whose construction failed with `status`: frees everything it owns by then (tr_bvh_destroy holds
+// that list) and keeps the message of the failure, which a failing hipFree in there would overwrite.
+static int handle_discard(tr_bvh* bvh, int status) {
+    const std::string msg = g_last_error;
+    (void)tr_bvh_destroy(bvh);
+    g_last_error = msg;
+    return status;
+}
+
 extern "C" {
 
 int tr_abi_version(void) { return TR_ABI_VERSION; }
@@ -187,18 +205,11 @@ int tr_bvh_build(const float* d_vertices, int64_t nv, const int32_t* d_faces, in
     tr_device_state* st;
     TR_TRY(tr_get_device_state(device, &st));
     tr_device_guard g;
-    if (g.enter(device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
-    tr_bvh* bvh = new (std::nothrow) tr_bvh();
+    TR_TRY(tr_enter_device(&g, device));
+    tr_bvh* bvh = handle_new(device);
     if (!bvh) return tr_fail(TR_ERR_OUT_OF_MEMORY, "host allocation failed");
-    bvh->device = device;
-    bvh->sched_mutex = new (std::nothrow) std::mutex();
-    int s = tr_build_impl(bvh, d_vertices, nv, d_faces, nf, (hipStream_t)stream);
-    if (s != TR_OK) {
-        if (bvh->arena) (void)hipFree(bvh->arena);
-        delete bvh->sched_mutex;
-        delete bvh;
-        return s;
-    }
+    const int s = tr_build_impl(bvh, d_vertices, nv, d_faces, nf, (hipStream_t)stream);
+    if (s != TR_OK) return handle_discard(bvh, s);
     *out = bvh;
     return TR_OK;
 }
@@ -207,7 +218,7 @@ int tr_bvh_update(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_
                   int64_t nf, void* stream) {
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     const int s = tr_build_impl(bvh, d_vertices, nv, d_faces, nf, (hipStream_t)stream);
     // a handle that has walked 8-wide nodes gets them rebuilt at once, in place where they fit: a HIP graph that
     // captured a wide launch keeps reading current geometry (as it does with the arena's nodes)
@@ -219,7 +230,7 @@ int tr_bvh_refit(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_t
                  int64_t nf, void* stream) {
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     const int s = tr_refit_impl(bvh, d_vertices, nv, d_faces, nf, (hipStream_t)stream);
     if (s == TR_OK) tr_wide_rebuild(bvh, (hipStream_t)stream);       // (same topology: same records, new boxes, same buffer)
     return s;
@@ -248,7 +259,7 @@ int tr_bvh_serialize(const tr_bvh* bvh, void* h_buffer, int64_t size, void* stre
     if (!bvh || !h_buffer) return tr_fail(TR_ERR_INVALID_ARG, "null argument");
     if (size < tr_bvh_serialized_size(bvh)) return tr_fail(TR_ERR_INVALID_ARG, "buffer too small");
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     tr_blob_header h;
     memset(&h, 0, sizeof h);
     memcpy(h.magic, TR_MAGIC, 8);
@@ -281,10 +292,8 @@ int tr_bvh_deserialize(const void* h_buffer, int64_t size, void* stream, tr_bvh*
         return tr_fail(TR_ERR_NO_DEVICE, "no HIP device available (libtriro_hip has no CPU fallback)");
     tr_device_state* st;
     TR_TRY(tr_get_device_state(device, &st));
-    tr_bvh* bvh = new (std::nothrow) tr_bvh();
+    tr_bvh* bvh = handle_new(device);
     if (!bvh) return tr_fail(TR_ERR_OUT_OF_MEMORY, "host allocation failed");
-    bvh->device = device;
-    bvh->sched_mutex = new (std::nothrow) std::mutex();
     // an empty build gives the handle a correctly carved arena of the right capacity
     int s = tr_build_impl(bvh, nullptr, 0, nullptr, 0, (hipStream_t)stream);
     if (s == TR_OK && h.num_tris > 0) {
@@ -302,12 +311,7 @@ int tr_bvh_deserialize(const void* h_buffer, int64_t size, void* stream, tr_bvh*
             s = tr_bvh_sync_frame(bvh);
         }
     }
-    if (s != TR_OK) {
-        if (bvh->arena) (void)hipFree(bvh->arena);
-        delete bvh->sched_mutex;
-        delete bvh;
-        return s;
-    }
+    if (s != TR_OK) return handle_discard(bvh, s);
     *out = bvh;
     return TR_OK;
 }
@@ -339,7 +343,7 @@ int tr_bvh_destroy(tr_bvh* bvh) {
 int tr_bvh_replica_hash(const tr_bvh* bvh, uint64_t* h_hash, void* stream) {
     if (!bvh || !h_hash) return tr_fail(TR_ERR_INVALID_ARG, "null argument");
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     tr_device_state* st;
     TR_TRY(tr_get_device_state(bvh->device, &st));
     hipStream_t s = (hipStream_t)stream;
@@ -402,7 +406,7 @@ int tr_bvh_download_qnodes(const tr_bvh* bvh, void* h_qnodes, float* h_frame6, v
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
     hipStream_t s = (hipStream_t)stream;
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     if (h_qnodes && bvh->num_nodes)
         TR_HIP_TRY(hipMemcpyAsync(h_qnodes, bvh->qnodes, sizeof(tr_qnode) * (size_t)bvh->num_nodes, hipMemcpyDeviceToHost, s));
     TR_HIP_TRY(hipStreamSynchronize(s));
@@ -415,7 +419,7 @@ int tr_bvh_download(const tr_bvh* bvh, void* h_nodes, void* h_links, void* h_tri
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
     hipStream_t s = (hipStream_t)stream;
     tr_device_guard g;
-    if (g.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&g, bvh->device));
     if (h_nodes && bvh->num_nodes)
         TR_HIP_TRY(hipMemcpyAsync(h_nodes, bvh->nodes, sizeof(tr_node) * (size_t)bvh->num_nodes, hipMemcpyDeviceToHost, s));
     if (h_links && bvh->num_nodes)

@@ -515,6 +515,194 @@ void tr_bvh_reset(tr_bvh* bvh) {
     for (int k = 0; k < TR_SCHED_SLOTS; k++) { bvh->sched[k].nblocks = 0; }
 }
 
+// ---- what build and refit share ---------------------------------------------------------------
+constexpr int TB = 256;                       // threads per workgroup of the one-thread-per-item kernels
+constexpr uint32_t NO_FACE = 0xffffffffu;     // the bad-face word while no face has an index outside [0, nv)
+
+// the first error wins; later steps are still enqueued, so that the streams are drained in one place
+static void check(int* status, hipError_t e, const char* what) {
+    if (e != hipSuccess && *status == TR_OK)
+        *status = tr_fail(TR_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e));
+}
+
+static int bad_face(uint32_t face, int64_t nv) {
+    return tr_fail(TR_ERR_INVALID_ARG, "face " + std::to_string(face) + " has a vertex index outside [0, " +
+                                           std::to_string(nv) + ")");
+}
+
+// A build or refit that failed with `status`: never leave a half-written hierarchy reachable (keep the error message)
+static int fail_reset(tr_bvh* bvh, int status) {
+    const std::string msg = tr_last_error();
+    tr_bvh_reset(bvh);
+    tr_set_error(msg);
+    return status;
+}
+
+// the mesh bounds, the grid frame they imply (== k_qframe's: same function, same bounds) and its copy on the device
+static int set_bounds(tr_bvh* bvh, const float lo[3], const float hi[3]) {
+    for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = lo[k]; bvh->aabb_max[k] = hi[k]; }
+    tr_qframe_make(bvh->aabb_min, bvh->aabb_max, &bvh->frame);
+    return tr_bvh_sync_frame(bvh) == TR_OK ? TR_OK : TR_ERR_HIP;
+}
+
+// ---- build ------------------------------------------------------------------------------------
+// The builder's temporaries: one allocation (tr_build_temp_acquire), about 130 B per triangle
+struct build_temps {
+    float *tribox, *sbox, *ibox;
+    uint64_t *k0, *k1;
+    uint32_t *v0, *v1, *hist, *gtot, *bounds;   // bounds: 8 words of bounds / flags + the quantisation frame (6 floats)
+    tr_qframe* frame;                           // ... that frame: bounds + 8
+    int32_t *cl, *cr, *par, *ready;
+    int32_t *span, *lpos, *lbase, *lflag;       // node layout: one carve of 4 nf words
+};
+
+// Their layout for `nf` triangles; returns total bytes and sets the pointers (to nothing while base == 0: the size only)
+static size_t carve_build_temps(build_temps* t, char* base, int64_t nf) {
+    Carver c{base};
+    t->tribox = c.take<float>(6 * (size_t)nf);
+    t->sbox = c.take<float>(6 * (size_t)nf);
+    t->ibox = c.take<float>(6 * (size_t)nf);
+    t->k0 = c.take<uint64_t>((size_t)nf);
+    t->k1 = c.take<uint64_t>((size_t)nf);
+    t->v0 = c.take<uint32_t>((size_t)nf);
+    t->v1 = c.take<uint32_t>((size_t)nf);
+    t->hist = c.take<uint32_t>(256 * (size_t)cdiv(nf, RS_TILE));
+    t->gtot = c.take<uint32_t>(8 * 256);
+    t->bounds = c.take<uint32_t>(8 + 8);
+    t->cl = c.take<int32_t>((size_t)nf);
+    t->cr = c.take<int32_t>((size_t)nf);
+    t->par = c.take<int32_t>((size_t)nf);
+    t->ready = c.take<int32_t>((size_t)nf);
+    t->span = c.take<int32_t>(4 * (size_t)nf);       // span | pos | bases | flag
+    if (base) {
+        t->lpos = t->span + nf; t->lbase = t->span + 2 * nf; t->lflag = t->span + 3 * nf;
+        t->frame = reinterpret_cast<tr_qframe*>(t->bounds + 8);
+    }
+    return align_up(c.off, 256);
+}
+
+// What the hierarchy is built over: per-triangle boxes, the mesh bounds / bad-face word (hb = their 7 words on the host
+// once the stream has been synchronised) and the grid frame; Morton codes, sorted (LSD radix sort, 8 passes of 8 bits);
+// the triangle records + boxes in that order.  A single triangle needs no sort, but its k_morton still runs: v0 feeds
+// k_gather.
+static void enqueue_triangles(tr_tri* tris, const build_temps& t, const float* d_vertices, int64_t nv, const int32_t* d_faces,
+                              int64_t nf, uint32_t* hb, hipStream_t stream, int* status) {
+    const unsigned gF = (unsigned)cdiv(nf, TB);
+    hipLaunchKernelGGL(k_init_bounds, dim3(1), dim3(64), 0, stream, t.bounds);
+    hipLaunchKernelGGL(k_tri_bounds, dim3(gF < 1024u ? gF : 1024u), dim3(TB), 0, stream, d_vertices, nv, d_faces, nf, t.tribox, t.bounds);
+    hipLaunchKernelGGL(k_qframe, dim3(1), dim3(64), 0, stream, t.bounds, t.frame);
+    check(status, hipGetLastError(), "k_tri_bounds");
+    check(status, hipMemcpyAsync(hb, t.bounds, sizeof(uint32_t) * 7, hipMemcpyDeviceToHost, stream), "memcpy bounds");
+
+    hipLaunchKernelGGL(k_morton, dim3(gF), dim3(TB), 0, stream, t.tribox, nf, t.bounds, t.k0, t.v0);
+    if (nf > 1) {
+        check(status, hipGetLastError(), "k_morton");
+        const int64_t ntiles = cdiv(nf, RS_TILE);
+        const unsigned gT = (unsigned)cdiv(ntiles, RS_WAVES);
+        uint64_t* kin = t.k0; uint64_t* kout = t.k1; uint32_t* vin = t.v0; uint32_t* vout = t.v1;
+        check(status, hipMemsetAsync(t.gtot, 0, sizeof(uint32_t) * 8 * 256, stream), "memset digit totals");
+        for (int pass = 0; pass < 8; pass++) {
+            int shift = 8 * pass;
+            hipLaunchKernelGGL(k_rs_count, dim3(gT), dim3(64 * RS_WAVES), 0, stream, kin, nf, shift, ntiles, t.hist, t.gtot + 256 * pass);
+            hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, stream, t.hist, ntiles, t.gtot + 256 * pass);
+            hipLaunchKernelGGL(k_rs_scatter, dim3(gT), dim3(64 * RS_WAVES), 0, stream, kin, vin, nf, shift,
+                               ntiles, t.hist, kout, vout);
+            uint64_t* tk = kin; kin = kout; kout = tk;
+            uint32_t* tv = vin; vin = vout; vout = tv;
+        }
+        check(status, hipGetLastError(), "radix sort");
+    }
+    // (after an even number of passes the sorted data is back in (k0, v0))
+    hipLaunchKernelGGL(k_gather, dim3(gF), dim3(TB), 0, stream, d_vertices, nv, d_faces, t.v0, nf, tris, t.sbox);
+    check(status, hipGetLastError(), "k_gather");
+}
+
+// Node layout (top-down, one launch per treelet level) on the builder's side stream, beside the refit rounds
+// (bottom-up) on the caller's: both need only the Karras hierarchy; the first emit waits for both (build_join).
+// As many levels as the guessed height needs -- returns their number; a higher tree gets the rest on the caller's stream.
+static int32_t fork_layout(tr_device_state* st, const build_temps& t, int64_t ni, int32_t guess, hipStream_t stream, int* status) {
+    check(status, hipEventRecord(st->build_fork, stream), "record fork");
+    check(status, hipStreamWaitEvent(st->build_side, st->build_fork, 0), "side waits");
+    check(status, hipMemsetAsync(t.lflag, 0, sizeof(int32_t) * (size_t)ni, st->build_side), "memset layout flags");
+    check(status, hipMemsetAsync(t.lpos, 0xff, sizeof(int32_t) * (size_t)ni, st->build_side), "memset layout positions");
+    hipLaunchKernelGGL(k_layout_init, dim3(1), dim3(64), 0, st->build_side, t.lbase, t.lflag);
+    const unsigned gI = (unsigned)cdiv(ni, TB);
+    int32_t lround = 0;
+    while (lround * TR_TREELET_LEVELS < guess + TR_TREELET_LEVELS) {
+        ++lround;
+        hipLaunchKernelGGL(k_layout_round, dim3(gI), dim3(TB), 0, st->build_side, t.cl, t.cr, t.span, t.lpos, t.lbase, t.lflag, ni, lround);
+    }
+    check(status, hipGetLastError(), "k_layout_round");
+    check(status, hipEventRecord(st->build_join, st->build_side), "record join");
+    return lround;
+}
+
+// One attempt at the hierarchy over the sorted keys, plain (mode 0) or depth-bounded (mode 1).  Speculative schedule:
+// enqueue `guess` refit rounds and k_emit, then read the root's round back ONCE; batches of 8 rounds follow only if
+// the root was not reached.  Returns the root's round = the height of the tree, 0 if it was not reached (or the mesh
+// turned out malformed: *bad_face, valid after each synchronisation).
+static int32_t try_hierarchy(tr_bvh* bvh, tr_device_state* st, const build_temps& t, int64_t nf, int mode, int32_t guess,
+                             bool treelets, const uint32_t* bad_face, hipStream_t stream, int* status) {
+    const int64_t ni = nf - 1;
+    const unsigned gI = (unsigned)cdiv(ni, TB);
+    if (mode == 0)
+        hipLaunchKernelGGL(k_karras<0>, dim3(gI), dim3(TB), 0, stream, t.k0, nf, t.cl, t.cr, t.par, t.span);
+    else
+        hipLaunchKernelGGL(k_karras<1>, dim3(gI), dim3(TB), 0, stream, t.k0, nf, t.cl, t.cr, t.par, t.span);
+    check(status, hipGetLastError(), "k_karras");
+    check(status, hipMemsetAsync(t.ready, 0, sizeof(int32_t) * (size_t)ni, stream), "memset ready");
+    int32_t lround = treelets ? fork_layout(st, t, ni, guess, stream, status) : 0;   // treelet levels laid out so far
+    bool lay_joined = !treelets;
+    int32_t root_ready = 0;
+    int32_t round = 0;
+    const int32_t max_rounds = 160;   // > 64 + 32 + slack
+    int32_t batch = guess;
+    while (root_ready == 0 && round < max_rounds && *status == TR_OK) {
+        for (int k = 0; k < batch; k++) {
+            ++round;
+            hipLaunchKernelGGL(k_refit_round, dim3(gI), dim3(TB), 0, stream, t.cl, t.cr, t.sbox, t.ibox, t.ready, ni, round);
+        }
+        check(status, hipGetLastError(), "k_refit_round");
+        // the layout needs one round per TR_TREELET_LEVELS levels; the tree is at most `round` high
+        // if its root has been reached (if not, both loops continue with the next batch)
+        if (!lay_joined) { check(status, hipStreamWaitEvent(stream, st->build_join, 0), "join layout"); lay_joined = true; }
+        while (treelets && lround * TR_TREELET_LEVELS < round + TR_TREELET_LEVELS) {
+            ++lround;
+            hipLaunchKernelGGL(k_layout_round, dim3(gI), dim3(TB), 0, stream, t.cl, t.cr, t.span, t.lpos, t.lbase, t.lflag, ni, lround);
+        }
+        // harmless if the root is not final yet: it is launched again after the next batch
+        hipLaunchKernelGGL(k_emit, dim3(gI), dim3(TB), 0, stream, t.cl, t.cr, t.par, t.sbox, t.ibox, ni, t.frame,
+                           treelets ? t.lpos : nullptr, bvh->nodes, bvh->links, bvh->qnodes);
+        check(status, hipGetLastError(), "k_emit");
+        check(status, hipMemcpyAsync(&root_ready, t.ready, sizeof(int32_t), hipMemcpyDeviceToHost, stream), "memcpy root");
+        check(status, hipStreamSynchronize(stream), "sync refit");
+        if (*bad_face != NO_FACE) return 0;
+        batch = 8;
+    }
+    return root_ready;
+}
+
+// Karras hierarchy, boxes and traversal nodes of nf >= 2 sorted triangles; sets bvh->depth and bvh->key_mode.  A tree
+// higher than 64 with plain keys is built again with depth-bounded ones.  Leaves a malformed mesh (*bad_face) to the
+// caller, which reports it once the streams have drained.
+static void build_hierarchy(tr_bvh* bvh, tr_device_state* st, const build_temps& t, int64_t nf, bool treelets,
+                            const uint32_t* bad_face, hipStream_t stream, int* status) {
+    // refit rounds the tree is expected to need: the previous build's height for a rebuild, log2(n) + 10 otherwise
+    int32_t guess = bvh->depth > 0 ? bvh->depth + 1 : 10;
+    if (bvh->depth <= 0) for (int64_t m = 1; m < nf; m <<= 1) ++guess;
+    if (guess > 64) guess = 64;
+    bvh->depth = 0;
+    for (int mode = 0; mode < 2 && *status == TR_OK; mode++) {
+        const int32_t height = try_hierarchy(bvh, st, t, nf, mode, guess, treelets, bad_face, stream, status);
+        if (*status != TR_OK || *bad_face != NO_FACE) return;
+        if (height == 0) { *status = tr_fail(TR_ERR_INTERNAL, "refit did not reach the root"); return; }
+        bvh->depth = height;
+        bvh->key_mode = mode;
+        if (height <= 64) return;
+        if (mode == 1) *status = tr_fail(TR_ERR_INTERNAL, "tree height > 64 with bounded keys");
+    }
+}
+
 int tr_build_impl(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_t* d_faces,
                   int64_t nf, hipStream_t stream) {
     if (nf < 0 || nv < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative mesh size");
@@ -523,204 +711,73 @@ int tr_build_impl(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_
     // an empty vertex array may be NULL: every face is then out of range and reported as such
     if (nf > 0 && (!d_faces || (!d_vertices && nv > 0))) return tr_fail(TR_ERR_INVALID_ARG, "null mesh pointer");
 
-    {
-        const int as = tr_arena_alloc(bvh, nf);
-        if (as != TR_OK) {
-            const std::string msg = tr_last_error();
-            tr_bvh_reset(bvh);
-            tr_set_error(msg);
-            return as;
-        }
-    }
-    bvh->num_tris = nf;
-    bvh->num_nodes = nf >= 2 ? nf - 1 : 0;
-    bvh->depth = 0;
-    bvh->key_mode = 0;
-    // A learned launch order describes the rays, not the mesh: after a rebuild (an animation step,
-    // `update_raw`) it is one frame stale, which is a far better hint than none -- keep it and
-    // measure again on the next launches (a deferred sort of the last measurement, if one is pending, runs before them:
-    // sched_acquire)
-    for (int k = 0; k < TR_SCHED_SLOTS; k++) { bvh->sched[k].launches = 0; }
-    for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = 0.f; bvh->aabb_max[k] = 0.f; }
-    if (nf == 0) return TR_OK;
-
-    // temporaries: one allocation
-    const int64_t ntiles = cdiv(nf, RS_TILE);
-    Carver tc{nullptr};
-    auto plan = [&](Carver& c, float*& tribox, float*& sbox, float*& ibox, uint64_t*& k0,
-                    uint64_t*& k1, uint32_t*& v0, uint32_t*& v1, uint32_t*& hist,
-                    uint32_t*& gtot, uint32_t*& bounds, int32_t*& cl, int32_t*& cr, int32_t*& par, int32_t*& ready,
-                    int32_t*& lay) {
-        tribox = c.take<float>(6 * (size_t)nf);
-        sbox = c.take<float>(6 * (size_t)nf);
-        ibox = c.take<float>(6 * (size_t)nf);
-        k0 = c.take<uint64_t>((size_t)nf);
-        k1 = c.take<uint64_t>((size_t)nf);
-        v0 = c.take<uint32_t>((size_t)nf);
-        v1 = c.take<uint32_t>((size_t)nf);
-        hist = c.take<uint32_t>(256 * (size_t)ntiles);
-        gtot = c.take<uint32_t>(8 * 256);
-        bounds = c.take<uint32_t>(8 + 8);   // 8 words of bounds / flags + the quantisation frame (6 floats)
-        cl = c.take<int32_t>((size_t)nf);
-        cr = c.take<int32_t>((size_t)nf);
-        par = c.take<int32_t>((size_t)nf);
-        ready = c.take<int32_t>((size_t)nf);
-        lay = c.take<int32_t>(4 * (size_t)nf);      // node layout: span | pos | bases | flag
-    };
-    float *tribox, *sbox, *ibox; uint64_t *k0, *k1; uint32_t *v0, *v1, *hist, *gtot, *bounds;
-    int32_t *cl, *cr, *par, *ready, *lay;
-    plan(tc, tribox, sbox, ibox, k0, k1, v0, v1, hist, gtot, bounds, cl, cr, par, ready, lay);
-    tr_device_state* st;
-    TR_TRY(tr_get_device_state(bvh->device, &st));
-    void* temp = nullptr;
-    TR_TRY(tr_build_temp_acquire(st, align_up(tc.off, 256), &temp));   // holds st->build_mutex
-    Carver tc2{(char*)temp};
-    plan(tc2, tribox, sbox, ibox, k0, k1, v0, v1, hist, gtot, bounds, cl, cr, par, ready, lay);
-    int32_t* span = lay; int32_t* lpos = lay + nf; int32_t* lbase = lay + 2 * nf; int32_t* lflag = lay + 3 * nf;
-    const bool treelets = tr_opts().node_layout != 0;
-
-    int status = TR_OK;
-    auto check = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && status == TR_OK)
-            status = tr_fail(TR_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e));
-    };
-    const int TB = 256;
-    const unsigned gF = (unsigned)cdiv(nf, TB);
-
-    tr_qframe* d_frame = reinterpret_cast<tr_qframe*>(bounds + 8);
-    hipLaunchKernelGGL(k_init_bounds, dim3(1), dim3(64), 0, stream, bounds);
-    hipLaunchKernelGGL(k_tri_bounds, dim3(gF < 1024u ? gF : 1024u), dim3(TB), 0, stream, d_vertices, nv, d_faces, nf, tribox, bounds);
-    hipLaunchKernelGGL(k_qframe, dim3(1), dim3(64), 0, stream, bounds, d_frame);
-    check(hipGetLastError(), "k_tri_bounds");
-    // mesh bounds back to the host; completes with the first synchronisation below
-    uint32_t hb[8] = {0};
-    hb[6] = 0xffffffffu;
-    check(hipMemcpyAsync(hb, bounds, sizeof(uint32_t) * 7, hipMemcpyDeviceToHost, stream), "memcpy bounds");
-
-    if (nf == 1) {
-        // single triangle: no hierarchy; queries use the brute-force kernel
-        hipLaunchKernelGGL(k_morton, dim3(gF), dim3(TB), 0, stream, tribox, nf, bounds, k0, v0);
-        hipLaunchKernelGGL(k_gather, dim3(gF), dim3(TB), 0, stream, d_vertices, nv, d_faces, v0, nf, bvh->tris, sbox);
-        check(hipGetLastError(), "k_gather");
-    } else {
-        hipLaunchKernelGGL(k_morton, dim3(gF), dim3(TB), 0, stream, tribox, nf, bounds, k0, v0);
-        check(hipGetLastError(), "k_morton");
-        uint64_t* kin = k0; uint64_t* kout = k1; uint32_t* vin = v0; uint32_t* vout = v1;
-        const unsigned gT = (unsigned)cdiv(ntiles, RS_WAVES);
-        check(hipMemsetAsync(gtot, 0, sizeof(uint32_t) * 8 * 256, stream), "memset digit totals");
-        for (int pass = 0; pass < 8; pass++) {
-            int shift = 8 * pass;
-            hipLaunchKernelGGL(k_rs_count, dim3(gT), dim3(64 * RS_WAVES), 0, stream, kin, nf, shift, ntiles, hist, gtot + 256 * pass);
-            hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, stream, hist, ntiles, gtot + 256 * pass);
-            hipLaunchKernelGGL(k_rs_scatter, dim3(gT), dim3(64 * RS_WAVES), 0, stream, kin, vin, nf, shift,
-                               ntiles, hist, kout, vout);
-            uint64_t* tk = kin; kin = kout; kout = tk;
-            uint32_t* tv = vin; vin = vout; vout = tv;
-        }
-        check(hipGetLastError(), "radix sort");
-        // after 8 passes the sorted data is back in (k0, v0) == (kin, vin)
-        hipLaunchKernelGGL(k_gather, dim3(gF), dim3(TB), 0, stream, d_vertices, nv, d_faces, vin, nf, bvh->tris, sbox);
-        check(hipGetLastError(), "k_gather");
-
-        const int64_t ni = nf - 1;
-        const unsigned gI = (unsigned)cdiv(ni, TB);
-        // Speculative schedule: enqueue the number of refit rounds the tree is expected to need
-        // (the previous build's height for a rebuild, log2(n)+10 otherwise) and k_emit, then
-        // read the root's round back ONCE.  More rounds follow only if the root was not reached.
-        int32_t guess = bvh->depth > 0 ? bvh->depth + 1 : 10;
-        if (bvh->depth <= 0) for (int64_t m = 1; m < nf; m <<= 1) ++guess;
-        if (guess > 64) guess = 64;
-        bvh->depth = 0;
-        for (int mode = 0; mode < 2 && status == TR_OK; mode++) {
-            if (mode == 0)
-                hipLaunchKernelGGL(k_karras<0>, dim3(gI), dim3(TB), 0, stream, kin, nf, cl, cr, par, span);
-            else
-                hipLaunchKernelGGL(k_karras<1>, dim3(gI), dim3(TB), 0, stream, kin, nf, cl, cr, par, span);
-            check(hipGetLastError(), "k_karras");
-            check(hipMemsetAsync(ready, 0, sizeof(int32_t) * (size_t)ni, stream), "memset ready");
-            // Node layout (top-down, one launch per treelet level) on the builder's side stream, beside
-            // the refit rounds (bottom-up) on the caller's: both need only the Karras hierarchy; the first
-            // emit waits for both.  As many levels as the guessed height needs; a higher tree gets the
-            // rest on the caller's stream further down.
-            int32_t lround = 0;              // treelet levels laid out so far
-            bool lay_joined = true;
-            if (treelets) {
-                check(hipEventRecord(st->build_fork, stream), "record fork");
-                check(hipStreamWaitEvent(st->build_side, st->build_fork, 0), "side waits");
-                check(hipMemsetAsync(lflag, 0, sizeof(int32_t) * (size_t)ni, st->build_side), "memset layout flags");
-                check(hipMemsetAsync(lpos, 0xff, sizeof(int32_t) * (size_t)ni, st->build_side), "memset layout positions");
-                hipLaunchKernelGGL(k_layout_init, dim3(1), dim3(64), 0, st->build_side, lbase, lflag);
-                while (lround * TR_TREELET_LEVELS < guess + TR_TREELET_LEVELS) {
-                    ++lround;
-                    hipLaunchKernelGGL(k_layout_round, dim3(gI), dim3(TB), 0, st->build_side, cl, cr, span, lpos, lbase, lflag, ni, lround);
-                }
-                check(hipGetLastError(), "k_layout_round");
-                check(hipEventRecord(st->build_join, st->build_side), "record join");
-                lay_joined = false;
-            }
-            int32_t root_ready = 0;
-            int32_t round = 0;
-            const int32_t max_rounds = 160;   // > 64 + 32 + slack
-            int32_t batch = guess;
-            while (root_ready == 0 && round < max_rounds && status == TR_OK) {
-                for (int k = 0; k < batch; k++) {
-                    ++round;
-                    hipLaunchKernelGGL(k_refit_round, dim3(gI), dim3(TB), 0, stream, cl, cr, sbox, ibox, ready, ni, round);
-                }
-                check(hipGetLastError(), "k_refit_round");
-                // the layout needs one round per TR_TREELET_LEVELS levels; the tree is at most `round` high
-                // if its root has been reached (if not, both loops continue below)
-                if (!lay_joined) { check(hipStreamWaitEvent(stream, st->build_join, 0), "join layout"); lay_joined = true; }
-                while (treelets && lround * TR_TREELET_LEVELS < round + TR_TREELET_LEVELS) {
-                    ++lround;
-                    hipLaunchKernelGGL(k_layout_round, dim3(gI), dim3(TB), 0, stream, cl, cr, span, lpos, lbase, lflag, ni, lround);
-                }
-                // harmless if the root is not final yet: it is launched again below
-                hipLaunchKernelGGL(k_emit, dim3(gI), dim3(TB), 0, stream, cl, cr, par, sbox, ibox, ni, d_frame,
-                                   treelets ? lpos : nullptr, bvh->nodes, bvh->links, bvh->qnodes);
-                check(hipGetLastError(), "k_emit");
-                check(hipMemcpyAsync(&root_ready, ready, sizeof(int32_t), hipMemcpyDeviceToHost, stream), "memcpy root");
-                check(hipStreamSynchronize(stream), "sync refit");
-                if (status == TR_OK && hb[6] != 0xffffffffu) break;   // malformed mesh: reported below
-                batch = 8;
-            }
-            if (hb[6] != 0xffffffffu) break;
-            if (status != TR_OK) break;
-            if (root_ready == 0) { status = tr_fail(TR_ERR_INTERNAL, "refit did not reach the root"); break; }
-            bvh->depth = root_ready;
-            bvh->key_mode = mode;
-            if (root_ready <= 64) break;
-            if (mode == 1) { status = tr_fail(TR_ERR_INTERNAL, "tree height > 64 with bounded keys"); break; }
-        }
-    }
-    // drain the streams before the temporaries are handed back (the side stream too: an error path may
-    // have left its layout rounds unjoined)
-    check(hipStreamSynchronize(stream), "sync build");
-    if (treelets) check(hipStreamSynchronize(st->build_side), "sync build side stream");
-    if (status == TR_OK && hb[6] != 0xffffffffu)
-        status = tr_fail(TR_ERR_INVALID_ARG, "face " + std::to_string(hb[6]) + " has a vertex index outside [0, " +
-                                                 std::to_string(nv) + ")");
+    // From here on there is one exit, which resets the handle on any failure: tr_arena_alloc may have replaced the
+    // arena with uninitialised memory, and the handle is about to claim `nf` triangles in it.
+    int status = tr_arena_alloc(bvh, nf);
     if (status == TR_OK) {
-        for (int k = 0; k < 3; k++) {
-            uint32_t e0 = hb[k], e1 = hb[3 + k];
-            uint32_t b0 = (e0 & 0x80000000u) ? (e0 & 0x7fffffffu) : ~e0;
-            uint32_t b1 = (e1 & 0x80000000u) ? (e1 & 0x7fffffffu) : ~e1;
-            memcpy(&bvh->aabb_min[k], &b0, 4);
-            memcpy(&bvh->aabb_max[k], &b1, 4);
+        bvh->num_tris = nf;
+        bvh->num_nodes = nf >= 2 ? nf - 1 : 0;
+        bvh->depth = 0;
+        bvh->key_mode = 0;
+        // A learned launch order describes the rays, not the mesh: after a rebuild (an animation step,
+        // `update_raw`) it is one frame stale, which is a far better hint than none -- keep it and
+        // measure again on the next launches (a deferred sort of the last measurement, if one is pending, runs before them:
+        // sched_acquire)
+        for (int k = 0; k < TR_SCHED_SLOTS; k++) { bvh->sched[k].launches = 0; }
+        for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = 0.f; bvh->aabb_max[k] = 0.f; }
+    }
+    tr_device_state* st = nullptr;
+    build_temps t;
+    void* temp = nullptr;
+    if (status == TR_OK && nf > 0) status = tr_get_device_state(bvh->device, &st);
+    if (status == TR_OK && nf > 0) status = tr_build_temp_acquire(st, carve_build_temps(&t, nullptr, nf), &temp);
+    if (status == TR_OK && nf > 0) {   // st->build_mutex is held down to tr_build_temp_release: no return in between
+        carve_build_temps(&t, (char*)temp, nf);
+        const bool treelets = tr_opts().node_layout != 0;
+        uint32_t hb[8] = {0};          // mesh bounds (ordered uints) and the bad-face word; complete with the first synchronisation
+        hb[6] = NO_FACE;
+        enqueue_triangles(bvh->tris, t, d_vertices, nv, d_faces, nf, hb, stream, &status);
+        // (a single triangle has no hierarchy; queries use the brute-force kernel)
+        if (nf > 1) build_hierarchy(bvh, st, t, nf, treelets, &hb[6], stream, &status);
+        // drain the streams before the temporaries are handed back (the side stream too: an error path may
+        // have left its layout rounds unjoined)
+        check(&status, hipStreamSynchronize(stream), "sync build");
+        if (treelets) check(&status, hipStreamSynchronize(st->build_side), "sync build side stream");
+        if (status == TR_OK && hb[6] != NO_FACE) status = bad_face(hb[6], nv);
+        if (status == TR_OK) {
+            float lo[3], hi[3];
+            for (int k = 0; k < 3; k++) {
+                uint32_t e0 = hb[k], e1 = hb[3 + k];
+                uint32_t b0 = (e0 & 0x80000000u) ? (e0 & 0x7fffffffu) : ~e0;
+                uint32_t b1 = (e1 & 0x80000000u) ? (e1 & 0x7fffffffu) : ~e1;
+                memcpy(&lo[k], &b0, 4);
+                memcpy(&hi[k], &b1, 4);
+            }
+            status = set_bounds(bvh, lo, hi);
         }
-        tr_qframe_make(bvh->aabb_min, bvh->aabb_max, &bvh->frame);   // == k_qframe's (same function, same bounds)
-        if (tr_bvh_sync_frame(bvh) != TR_OK && status == TR_OK) status = TR_ERR_HIP;
+        const int rs = tr_build_temp_release(st);   // the streams are drained: the next build may reuse the buffer
+        if (rs != TR_OK && status == TR_OK) status = rs;
     }
-    int rs = tr_build_temp_release(st);   // the stream is drained: the next build may reuse the buffer
-    if (rs != TR_OK && status == TR_OK) status = rs;
-    if (status != TR_OK) {   // never leave a half-built hierarchy reachable (keep the error message)
-        const std::string msg = tr_last_error();
-        tr_bvh_reset(bvh);
-        tr_set_error(msg);
-    }
-    return status;
+    return status == TR_OK ? TR_OK : fail_reset(bvh, status);
 }
 
+// ---- refit ------------------------------------------------------------------------------------
+// Its temporaries: boxes + flags, kept in the handle between calls (bvh->refit_temp)
+struct refit_temps {
+    float *sbox, *ibox;
+    int32_t* ready;
+    uint32_t* bad;          // smallest face id with an out-of-range vertex index | the quantisation frame (from word 4)
+};
+
+// Their layout for `nf` triangles under `ni` internal nodes; returns total bytes and sets the pointers (as above)
+static size_t carve_refit_temps(refit_temps* t, char* base, int64_t nf, int64_t ni) {
+    Carver c{base};
+    t->sbox = c.take<float>(6 * (size_t)nf);
+    t->ibox = c.take<float>(6 * (size_t)(ni > 0 ? ni : 1));
+    t->ready = c.take<int32_t>((size_t)(ni > 0 ? ni : 1));
+    t->bad = c.take<uint32_t>(4 + 8);
+    return align_up(c.off, 256);
+}
 
 // Refit: keep the hierarchy (Morton order, Karras topology), recompute every box from new
 // vertex positions.  No host synchronisation except the final one that orders the free of
@@ -733,65 +790,37 @@ int tr_refit_impl(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_
     if (!d_vertices || !d_faces) return tr_fail(TR_ERR_INVALID_ARG, "null mesh pointer");
     if (nv < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative mesh size");
     const int64_t ni = bvh->num_nodes;
-    Carver tc{nullptr};
-    tc.take<float>(6 * (size_t)nf); tc.take<float>(6 * (size_t)(ni > 0 ? ni : 1)); tc.take<int32_t>((size_t)(ni > 0 ? ni : 1));
-    tc.take<uint32_t>(4 + 8);
-    const size_t need = align_up(tc.off, 256);
+    refit_temps t;
+    const size_t need = carve_refit_temps(&t, nullptr, nf, ni);
     if (bvh->refit_temp_bytes < need) {
         if (bvh->refit_temp) { TR_HIP_TRY(hipFree(bvh->refit_temp)); bvh->refit_temp = nullptr; bvh->refit_temp_bytes = 0; }
         TR_HIP_TRY(hipMalloc(&bvh->refit_temp, need));
         bvh->refit_temp_bytes = need;
     }
-    Carver c2{(char*)bvh->refit_temp};
-    float* sbox = c2.take<float>(6 * (size_t)nf);
-    float* ibox = c2.take<float>(6 * (size_t)(ni > 0 ? ni : 1));
-    int32_t* ready = c2.take<int32_t>((size_t)(ni > 0 ? ni : 1));
-    uint32_t* bad = c2.take<uint32_t>(4 + 8);   // smallest face id with an out-of-range vertex index | frame
-    tr_qframe* d_frame = reinterpret_cast<tr_qframe*>(bad + 4);
-    uint32_t hbad = 0xffffffffu;
+    carve_refit_temps(&t, (char*)bvh->refit_temp, nf, ni);
+    tr_qframe* d_frame = reinterpret_cast<tr_qframe*>(t.bad + 4);
+    uint32_t hbad = NO_FACE;
     int status = TR_OK;
-    auto check = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && status == TR_OK)
-            status = tr_fail(TR_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e));
-    };
-    const int TB = 256;
-    check(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), stream), "memset bad-face word");
-    hipLaunchKernelGGL(k_regather, dim3((unsigned)cdiv(nf, TB)), dim3(TB), 0, stream, d_vertices, nv, d_faces, nf, bvh->tris, sbox, bad);
-    check(hipGetLastError(), "k_regather");
-    check(hipMemcpyAsync(&hbad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "memcpy bad-face word");
+    check(&status, hipMemsetAsync(t.bad, 0xff, sizeof(uint32_t), stream), "memset bad-face word");
+    hipLaunchKernelGGL(k_regather, dim3((unsigned)cdiv(nf, TB)), dim3(TB), 0, stream, d_vertices, nv, d_faces, nf, bvh->tris, t.sbox, t.bad);
+    check(&status, hipGetLastError(), "k_regather");
+    check(&status, hipMemcpyAsync(&hbad, t.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "memcpy bad-face word");
     if (ni > 0) {
         const unsigned gI = (unsigned)cdiv(ni, TB);
-        check(hipMemsetAsync(ready, 0, sizeof(int32_t) * (size_t)ni, stream), "memset ready");
+        check(&status, hipMemsetAsync(t.ready, 0, sizeof(int32_t) * (size_t)ni, stream), "memset ready");
         for (int32_t round = 1; round <= bvh->depth; round++)
-            hipLaunchKernelGGL(k_refit_nodes_round, dim3(gI), dim3(TB), 0, stream, bvh->nodes, sbox, ibox, ready, ni, round);
-        hipLaunchKernelGGL(k_qframe_box, dim3(1), dim3(64), 0, stream, ibox, d_frame);   // the new root box
-        hipLaunchKernelGGL(k_update_boxes, dim3(gI), dim3(TB), 0, stream, bvh->nodes, sbox, ibox, ni, d_frame, bvh->qnodes);
-        check(hipGetLastError(), "refit rounds");
-        float rootbox[6];
-        check(hipMemcpyAsync(rootbox, ibox, sizeof(rootbox), hipMemcpyDeviceToHost, stream), "memcpy root box");
-        check(hipStreamSynchronize(stream), "sync refit");
-        if (status == TR_OK) {
-            for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = rootbox[k]; bvh->aabb_max[k] = rootbox[3 + k]; }
-            tr_qframe_make(bvh->aabb_min, bvh->aabb_max, &bvh->frame);
-            if (tr_bvh_sync_frame(bvh) != TR_OK) status = TR_ERR_HIP;
-        }
-    } else {
-        float box[6];
-        check(hipMemcpyAsync(box, sbox, sizeof(box), hipMemcpyDeviceToHost, stream), "memcpy box");
-        check(hipStreamSynchronize(stream), "sync refit");
-        if (status == TR_OK) {
-            for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = box[k]; bvh->aabb_max[k] = box[3 + k]; }
-            tr_qframe_make(bvh->aabb_min, bvh->aabb_max, &bvh->frame);      // (the box rays are anchored to: also for one triangle)
-            if (tr_bvh_sync_frame(bvh) != TR_OK) status = TR_ERR_HIP;
-        }
+            hipLaunchKernelGGL(k_refit_nodes_round, dim3(gI), dim3(TB), 0, stream, bvh->nodes, t.sbox, t.ibox, t.ready, ni, round);
+        hipLaunchKernelGGL(k_qframe_box, dim3(1), dim3(64), 0, stream, t.ibox, d_frame);   // the new root box
+        hipLaunchKernelGGL(k_update_boxes, dim3(gI), dim3(TB), 0, stream, bvh->nodes, t.sbox, t.ibox, ni, d_frame, bvh->qnodes);
+        check(&status, hipGetLastError(), "refit rounds");
     }
-    if (status == TR_OK && hbad != 0xffffffffu)
-        status = tr_fail(TR_ERR_INVALID_ARG, "face " + std::to_string(hbad) + " has a vertex index outside [0, " +
-                                                 std::to_string(nv) + ")");
-    if (status != TR_OK) {   // the triangle records are partly rewritten: drop the hierarchy
-        const std::string msg = tr_last_error();
-        tr_bvh_reset(bvh);
-        tr_set_error(msg);
-    }
-    return status;
+    // the new bounds: the root's box, or the box of the single triangle (the box rays are anchored to: also for one triangle)
+    float box[6];
+    check(&status, hipMemcpyAsync(box, ni > 0 ? t.ibox : t.sbox, sizeof(box), hipMemcpyDeviceToHost, stream),
+          ni > 0 ? "memcpy root box" : "memcpy box");
+    check(&status, hipStreamSynchronize(stream), "sync refit");
+    if (status == TR_OK) status = set_bounds(bvh, box, box + 3);
+    if (status == TR_OK && hbad != NO_FACE) status = bad_face(hbad, nv);
+    // on failure the triangle records are partly rewritten: drop the hierarchy
+    return status == TR_OK ? TR_OK : fail_reset(bvh, status);
 }

@@ -169,6 +169,10 @@ struct tr_device_guard {
         if (changed) (void)hipSetDevice(prev);
     }
 };
+// ... and the preamble of such an entry point: tr_device_guard g; TR_TRY(tr_enter_device(&g, device));
+inline int tr_enter_device(tr_device_guard* g, int device) {
+    return g->enter(device) == TR_OK ? TR_OK : tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+}
 
 // options ---------------------------------------------------------------------------------
 // Process-wide tuning knobs (tr_set_option).  Stored as relaxed atomics; every entry point takes
