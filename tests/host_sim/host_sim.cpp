@@ -588,3 +588,18 @@ extern "C" void sim_tri_fast_vs_exact(const float* o, const float* d, const floa
         truth[i] = amb ? 2 : ((pos && neg) ? 0 : 1);
     }
 }
+
+// ---- the float64 edge functions themselves, pair by pair (tests/test_exact_cpu.py) -------------------------------------
+// For (ray i, triangle i): tr_woop64's U, V, W as the contract computes them, and tr_tie_code of them (whether or not the
+// triangle is hit) -- what the integer reference of tests/exact_ref.py is compared with: where float64 rounds an edge
+// function to zero that is not zero, and where it keeps one that lies within the rounding band.
+extern "C" void sim_woop_pairs(const float* o, const float* d, const float* tri, int64_t n, double* uvw, int32_t* code) {
+    for (int64_t i = 0; i < n; i++) {
+        const float* t = tri + 9 * i;
+        tr_woop w;
+        tr_woop64(o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2], t[0], t[1], t[2], t[3], t[4], t[5],
+                  t[6], t[7], t[8], w);
+        uvw[3 * i] = w.U; uvw[3 * i + 1] = w.V; uvw[3 * i + 2] = w.W;
+        code[i] = tr_tie_code(w, (w.U + w.V) + w.W);
+    }
+}

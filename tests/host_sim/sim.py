@@ -45,6 +45,7 @@ def lib():
         L.sim_check_fused.restype = C.c_int64
         L.sim_check_fused.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.sim_tri_fast_vs_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+        L.sim_woop_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -59,6 +60,15 @@ def tri_fast_vs_exact(o, d, tri):
     lib().sim_tri_fast_vs_exact(o.ctypes.data, d.ctypes.data, tri.ctypes.data, n, code.ctypes.data, tf.ctypes.data,
                                 he.ctypes.data, te.ctypes.data, truth.ctypes.data)
     return code, tf, he, te, truth
+
+
+def woop_pairs(o, d, tri):
+    """per (ray, triangle) pair: (tr_woop64's U, V, W [n, 3] float64, tr_tie_code of them [n])"""
+    o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+    tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
+    uvw, code = np.empty((len(o), 3), np.float64), np.empty(len(o), np.int32)
+    lib().sim_woop_pairs(o.ctypes.data, d.ctypes.data, tri.ctypes.data, len(o), uvw.ctypes.data, code.ctypes.data)
+    return uvw, code
 
 
 NODE_WORDS, LINK_WORDS, TRI_WORDS = 16, 2, 12
