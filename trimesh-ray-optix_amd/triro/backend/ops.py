@@ -736,3 +736,90 @@ def closest_point_native(accel_structure, points, stack_entries=0, want_closest=
                                     distance.data_ptr() if distance is not None else None, tri.data_ptr(),
                                     int(stack_entries), _stream_ptr(dev)))
     return closest, distance, tri
+
+
+# --- any / closest on a per-ray interval [tmin, tmax] (include/triro_range.h, csrc/range.hip) --------------------------
+_RANGE_LIB_NAME = "libtriro_range.so"
+RANGE_ABI_VERSION = 1    # TR_RANGE_ABI_VERSION of include/triro_range.h
+_range_module = None
+
+# every symbol include/triro_range.h declares: (restype, argtypes)
+RANGE_ABI = {
+    "tr_range_abi_version": (_int, []),
+    "tr_range_stack_capacity": (_int, []),
+    "tr_range_any": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _int, _vp]),
+    "tr_range_closest": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+def range_library_path() -> str:
+    return os.environ.get("TRIRO_RANGE_LIBRARY") or os.path.join(os.path.dirname(library_path()), _RANGE_LIB_NAME)
+
+
+def get_range_module():
+    """libtriro_range.so.  Raises when it is not built or does not match this binding."""
+    global _range_module
+    if _range_module is None:
+        get_module()                       # libtriro_hip.so first: the range library links against it
+        path = range_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in RANGE_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_range_abi_version() != RANGE_ABI_VERSION:
+            raise RuntimeError(f"libtriro_range.so ABI version {lib.tr_range_abi_version()} != {RANGE_ABI_VERSION} expected by this binding")
+        _range_module = lib
+    return _range_module
+
+
+def _range_bound(t, name, n, dev):
+    """a bound of the range queries: None (the default) or a dense float32 [n] tensor on the rays' device"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or \
+            tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be None or a contiguous float32 tensor of {n} elements on the rays' device")
+    return t
+
+
+def range_any_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
+    """tr_range_any: bool[*b], is anything hit within [tmin, tmax] (closed, measured from the origin given, no anchoring).
+    Rays as for intersects_any (any strides); tmin / tmax: None or dense float32 [n], n = the number of rays.
+    stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).  Nothing is allocated by the
+    library and nothing is synchronised."""
+    check_rays(origins, dirs)
+    lib = get_range_module()
+    dev, n = origins.device, origins.numel() // 3
+    handle = _handle(accel_structure, origins)
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    out = _new_output(origins.shape[:-1], torch.bool, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_range_any(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
+                                tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def range_closest_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0, want_t=True, want_dense=True):
+    """tr_range_closest: (hit bool[*b], front bool[*b], tri int32[*b], loc float32[*b, 3], uv float32[*b, 2], t float32[*b])
+    of the first hit within [tmin, tmax]; a miss is (False, False, -1, 0, 0, +Inf).  want_t=False: t is None;
+    want_dense=False: hit, front, loc and uv are None (tri, and t, alone).  Arguments as range_any_native."""
+    check_rays(origins, dirs)
+    lib = get_range_module()
+    b, dev, n = origins.shape[:-1], origins.device, origins.numel() // 3
+    handle = _handle(accel_structure, origins)
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    tri = _new_output(b, torch.int32, dev)
+    t = _new_output(b, torch.float32, dev) if want_t else None
+    hit = _new_output(b, torch.bool, dev) if want_dense else None
+    front = _new_output(b, torch.bool, dev) if want_dense else None
+    loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
+    uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
+    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_range_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), tri.data_ptr(), ptr(t), ptr(hit),
+                                    ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
+    return hit, front, tri, loc, uv, t

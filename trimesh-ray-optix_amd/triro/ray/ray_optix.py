@@ -320,6 +320,81 @@ class RayMeshIntersector:
         inside = self.contains_points(flat, check_direction)      # (keeps its [n, 3] quirk)
         return torch.where(inside, distance, -distance).reshape(b)
 
+    # -- ranges (optixTrace's tmin / tmax; not in the reference, which traces [0, 1e7] always) ------------------------
+    def _range_rays(self, origins, directions, tmin, tmax):
+        """(origins, directions, tmin, tmax) as the native range entries take them: float32 rays [*b, 3] on the
+        acceleration structure's GPU, bounds None or dense float32 [n]"""
+        dev = self.mesh_vertices.device
+        for name, x in (("origins", origins), ("directions", directions), ("tmin", tmin), ("tmax", tmax)):
+            if isinstance(x, torch.Tensor):
+                if name in ("origins", "directions") and not x.is_cuda:
+                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
+                if x.is_cuda and x.device != dev:
+                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
+                                     f"move it or build the intersector on that device")
+        o = origins if isinstance(origins, torch.Tensor) and origins.dtype == torch.float32 else _to_device_tensor(origins, torch.float32, dev)
+        d = directions if isinstance(directions, torch.Tensor) and directions.dtype == torch.float32 else _to_device_tensor(directions, torch.float32, dev)
+        if o.dim() < 1 or o.shape[-1] != 3 or o.shape != d.shape:
+            raise ValueError(f"origins and directions must have the same shape [*b, 3], got {tuple(o.shape)} and {tuple(d.shape)}")
+        b = o.shape[:-1]
+        bounds = []
+        for name, x in (("tmin", tmin), ("tmax", tmax)):
+            if x is None:
+                bounds.append(None)
+                continue
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, np.float32))
+            t = t.to(device=dev, dtype=torch.float32)
+            try:
+                t = t.broadcast_to(b)
+            except RuntimeError:
+                raise ValueError(f"{name} of shape {tuple(t.shape)} does not broadcast to the batch shape {tuple(b)}") from None
+            bounds.append(t.contiguous().reshape(-1))
+        return o, d, bounds[0], bounds[1]
+
+    def intersects_any_range(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
+        """Bool[*b]: is anything hit at a distance t (P = o + t d) with tmin <= t <= tmax, one launch of libtriro_range.so.
+        The interval is closed: a hit at exactly tmin or tmax counts.  Distances are measured from the origin given:
+        a range ray is never anchored.  tmin / tmax: None (0 / 1e7), a scalar or anything that broadcasts to [*b]."""
+        o, d, lo, hi = self._range_rays(origins, directions, tmin, tmax)
+        return hops.range_any_native(self.as_wrapper, o, d, lo, hi)
+
+    def intersects_closest_range(self, origins, directions, tmin=None, tmax=None):
+        """(hit[*b], front[*b], tri_idx[*b], loc[*b,3], uv[*b,2], t[*b]): the first hit with tmin <= t <= tmax, as
+        intersects_closest returns it, and its distance t (+Inf for a miss).  The interval is closed: a hit at exactly
+        tmin or tmax counts.  Distances are measured from the origin given: a range ray is never anchored."""
+        o, d, lo, hi = self._range_rays(origins, directions, tmin, tmax)
+        return hops.range_closest_native(self.as_wrapper, o, d, lo, hi)
+
+    def _segment_rays(self, p0, p1):
+        dev = self.mesh_vertices.device
+        for name, x in (("p0", p0), ("p1", p1)):
+            if isinstance(x, torch.Tensor) and not x.is_cuda:
+                raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
+            if isinstance(x, torch.Tensor) and x.device != dev:
+                raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
+                                 f"move it or build the intersector on that device")
+        a, b = _to_device_tensor(p0, torch.float32, dev), _to_device_tensor(p1, torch.float32, dev)
+        if a.dim() < 1 or a.shape[-1] != 3 or a.shape != b.shape:
+            raise ValueError(f"p0 and p1 must have the same shape [*b, 3], got {tuple(a.shape)} and {tuple(b.shape)}")
+        return a, b - a
+
+    def segments_any(self, p0, p1) -> torch.Tensor:
+        """Bool[*b]: is the segment from p0 to p1 blocked.  The ray (p0, the float32 p1 - p0) on the closed interval [0, 1]:
+        a surface exactly at either end blocks.  Measured from p0, never anchored."""
+        o, d = self._segment_rays(p0, p1)
+        n = o.numel() // 3
+        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        return hops.range_any_native(self.as_wrapper, o, d, None, one)
+
+    def segments_closest(self, p0, p1):
+        """(hit[*b], front[*b], tri_idx[*b], loc[*b,3], uv[*b,2], t[*b]): the first hit of the segment from p0 to p1; t
+        is the fraction along it.  The ray (p0, the float32 p1 - p0) on the closed interval [0, 1]: a hit at exactly
+        either end counts.  Measured from p0, never anchored."""
+        o, d = self._segment_rays(p0, p1)
+        n = o.numel() // 3
+        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        return hops.range_closest_native(self.as_wrapper, o, d, None, one)
+
     # -- extras (not in the reference) -------------------------------------------------------
     def bvh_info(self) -> dict:
         return self.as_wrapper.info()
