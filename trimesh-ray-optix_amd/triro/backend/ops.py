@@ -823,3 +823,129 @@ def range_closest_native(accel_structure, origins, dirs, tmin=None, tmax=None, s
         _check(lib.tr_range_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), tri.data_ptr(), ptr(t), ptr(hit),
                                     ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
     return hit, front, tri, loc, uv, t
+
+
+# --- any / closest over placed copies of several meshes (include/triro_scene.h, csrc/scene.hip) --------------------------
+_SCENE_LIB_NAME = "libtriro_scene.so"
+SCENE_ABI_VERSION = 1    # TR_SCENE_ABI_VERSION of include/triro_scene.h
+_scene_module = None
+
+
+class TrSceneInfo(C.Structure):
+    """tr_scene_info_t (include/triro_scene.h)"""
+    _fields_ = [("device", C.c_int32), ("stack_capacity", C.c_int32), ("num_members", C.c_int64), ("num_instances", C.c_int64),
+                ("valid_instances", C.c_int64), ("table_bytes", C.c_int64), ("commits", C.c_int64)]
+
+
+# every symbol include/triro_scene.h declares: (restype, argtypes)
+SCENE_ABI = {
+    "tr_scene_abi_version": (_int, []),
+    "tr_scene_create": (_int, [_int, C.POINTER(_vp)]),
+    "tr_scene_destroy": (_int, [_vp]),
+    "tr_scene_commit": (_int, [_vp, C.POINTER(_vp), _i64, _vp, _vp, _i64, _vp]),
+    "tr_scene_info": (_int, [_vp, C.POINTER(TrSceneInfo)]),
+    "tr_scene_any": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _int, _vp]),
+    "tr_scene_closest": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+def scene_library_path() -> str:
+    return os.environ.get("TRIRO_SCENE_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_LIB_NAME)
+
+
+def get_scene_module():
+    """libtriro_scene.so.  Raises when it is not built or does not match this binding."""
+    global _scene_module
+    if _scene_module is None:
+        get_module()                       # libtriro_hip.so first: the scene library links against it
+        path = scene_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in SCENE_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_scene_abi_version() != SCENE_ABI_VERSION:
+            raise RuntimeError(f"libtriro_scene.so ABI version {lib.tr_scene_abi_version()} != {SCENE_ABI_VERSION} expected by this binding")
+        _scene_module = lib
+    return _scene_module
+
+
+def scene_create(device_index: int) -> int:
+    """tr_scene_create: an empty scene on cuda:device_index; the handle (an integer) is the caller's to scene_destroy"""
+    handle = C.c_void_p()
+    _check(get_scene_module().tr_scene_create(int(device_index), C.byref(handle)))
+    return handle.value
+
+
+def scene_destroy(handle):
+    if handle:
+        get_scene_module().tr_scene_destroy(handle)
+
+
+def scene_commit(handle, member_handles, mesh_of_instance, transforms, device_index: int):
+    """tr_scene_commit: member_handles a list of tr_bvh* (integers), mesh_of_instance int32 [n] and transforms float32
+    [n, 12] HOST numpy arrays.  The one scene call that allocates, copies and synchronises (the current stream)."""
+    import numpy as np
+    mesh_of = np.ascontiguousarray(mesh_of_instance, np.int32).reshape(-1)
+    M = np.ascontiguousarray(transforms, np.float32).reshape(-1, 12)
+    if len(M) != len(mesh_of):
+        raise ValueError(f"{len(mesh_of)} instances but {len(M)} transforms")
+    for k, h in enumerate(member_handles):
+        if not h:
+            raise RuntimeError(f"member {k}: its acceleration structure has not been built")
+    members = (_vp * max(len(member_handles), 1))(*member_handles)
+    with torch.cuda.device(device_index):
+        _check(get_scene_module().tr_scene_commit(handle, members, len(member_handles), mesh_of.ctypes.data, M.ctypes.data, len(mesh_of),
+                                                  _stream_ptr(torch.device("cuda", device_index))))
+
+
+def scene_info(handle) -> dict:
+    inf = TrSceneInfo()
+    _check(get_scene_module().tr_scene_info(handle, C.byref(inf)))
+    return {k: int(getattr(inf, k)) for k, _ in inf._fields_}
+
+
+def _scene_rays(origins, dirs, device_index):
+    check_rays(origins, dirs)
+    if origins.device.index != device_index:
+        raise ValueError(f"rays are on {origins.device} but the scene lives on cuda:{device_index}; move the rays")
+
+
+def scene_any_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
+    """tr_scene_any: bool[*b], does any instance have a hit within [tmin, tmax] of the world ray.  Arguments as
+    range_any_native, with the scene handle and its device in place of the acceleration structure.  Nothing is allocated
+    by the library and nothing is synchronised."""
+    _scene_rays(origins, dirs, device_index)
+    lib = get_scene_module()
+    dev, n = origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    out = _new_output(origins.shape[:-1], torch.bool, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_any(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
+                                tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def scene_closest_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0, want_t=True, want_dense=True):
+    """tr_scene_closest: (hit bool[*b], front bool[*b], instance int32[*b], tri int32[*b], t float32[*b], loc float32[*b, 3],
+    uv float32[*b, 2]) of the first hit within [tmin, tmax] over all instances; a miss is (False, False, -1, -1, +Inf, 0, 0).
+    want_t=False: t is None; want_dense=False: hit, front, loc and uv are None (instance, tri and t alone)."""
+    _scene_rays(origins, dirs, device_index)
+    lib = get_scene_module()
+    b, dev, n = origins.shape[:-1], origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    inst = _new_output(b, torch.int32, dev)
+    tri = _new_output(b, torch.int32, dev)
+    t = _new_output(b, torch.float32, dev) if want_t else None
+    hit = _new_output(b, torch.bool, dev) if want_dense else None
+    front = _new_output(b, torch.bool, dev) if want_dense else None
+    loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
+    uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
+    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), inst.data_ptr(), tri.data_ptr(), ptr(t),
+                                    ptr(hit), ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
+    return hit, front, inst, tri, t, loc, uv

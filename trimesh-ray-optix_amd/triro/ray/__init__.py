@@ -13,3 +13,5 @@ hops.create_optix_context()
 hops.create_optix_module()
 hops.create_optix_pipelines()
 hops.build_sbts()
+
+from triro.ray.scene import RaySceneIntersector  # noqa: E402,F401  (instanced scenes: not in the reference)

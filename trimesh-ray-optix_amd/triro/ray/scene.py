@@ -1,0 +1,120 @@
+"""RaySceneIntersector -- ray queries over placed copies of several meshes (libtriro_scene.so, include/triro_scene.h).
+
+A scene holds references to RayMeshIntersector members and a list of instances: a member index and a placement, object
+to world, any invertible affine map.  One BVH serves every copy of a member, and moving an object is a commit of twelve
+floats, not a rebuild.  Distances are the world ray's own parameter (an affine map preserves it), so the answer is the
+minimum over the instances of the range query on the transformed ray: csrc/tr_scene.h has the contract.
+
+Not in the reference (which has one mesh in one coordinate system): what OptiX answers with instance acceleration
+structures."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+import triro.backend.ops as hops
+from triro.ray.ray_optix import RayMeshIntersector, _default_device
+
+
+def _transforms(transforms) -> np.ndarray:
+    """[n, 4, 4] (last row 0 0 0 1) or [n, 3, 4], a tensor or an array -> float32 [n, 12] on the host"""
+    t = transforms.detach().cpu().numpy() if isinstance(transforms, torch.Tensor) else np.asarray(transforms)
+    if t.size == 0 and t.ndim <= 1:
+        t = t.reshape(0, 3, 4)
+    if t.ndim != 3 or t.shape[1:] not in ((4, 4), (3, 4)):
+        raise ValueError(f"transforms must have shape [n, 4, 4] or [n, 3, 4], got {tuple(t.shape)}")
+    if t.shape[1] == 4:
+        if not (t[:, 3, :] == np.array([0, 0, 0, 1], t.dtype)).all():
+            raise ValueError("the last row of every [4, 4] transform must be 0 0 0 1 (placements are affine maps)")
+        t = t[:, :3, :]
+    return np.ascontiguousarray(t, np.float32).reshape(-1, 12)
+
+
+class RaySceneIntersector:
+    """RaySceneIntersector(meshes, mesh_of_instance, transforms): `meshes` a list of RayMeshIntersector on one GPU (held by
+    reference), instance k places meshes[mesh_of_instance[k]] by transforms[k] (object -> world)."""
+
+    def __init__(self, meshes, mesh_of_instance, transforms):
+        self.meshes = list(meshes)
+        for k, m in enumerate(self.meshes):
+            if not isinstance(m, RayMeshIntersector):
+                raise ValueError(f"meshes[{k}] is not a RayMeshIntersector")
+        # (no mesh at all is a scene too, as for the C entries: it has no instance and every ray misses)
+        self.device = self.meshes[0].mesh_vertices.device if self.meshes else _default_device()
+        for k, m in enumerate(self.meshes):
+            if m.mesh_vertices.device != self.device:
+                raise ValueError(f"meshes[{k}] lives on {m.mesh_vertices.device}, meshes[0] on {self.device}: a scene is on one device")
+        mesh_of = mesh_of_instance.detach().cpu().numpy() if isinstance(mesh_of_instance, torch.Tensor) else np.asarray(mesh_of_instance)
+        if mesh_of.ndim != 1 and mesh_of.size:
+            raise ValueError(f"mesh_of_instance must have shape [n], got {tuple(mesh_of.shape)}")
+        mesh_of = mesh_of.reshape(-1)
+        if mesh_of.size and not np.issubdtype(mesh_of.dtype, np.integer):
+            raise ValueError("mesh_of_instance must hold integers")
+        if mesh_of.size and (mesh_of.min() < 0 or mesh_of.max() >= len(self.meshes)):
+            raise ValueError(f"mesh_of_instance names a mesh outside [0, {len(self.meshes)})")
+        self.mesh_of_instance = mesh_of.astype(np.int32)
+        self._helper = RayMeshIntersector.__new__(RayMeshIntersector)      # the ray marshalling of the range methods, which reads the device only
+        self._helper.mesh_vertices = torch.empty((0, 3), dtype=torch.float32, device=self.device)
+        self.transforms = np.zeros((0, 12), np.float32)
+        self._handle = None
+        self._handle = hops.scene_create(self.device.index)
+        self.set_transforms(transforms)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                hops.scene_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    # -- the scene ---------------------------------------------------------------------------
+    def set_transforms(self, transforms):
+        """New placements for the same instances ([n, 4, 4] or [n, 3, 4]) and a commit: no member is rebuilt."""
+        M = _transforms(transforms)
+        if len(M) != len(self.mesh_of_instance):
+            raise ValueError(f"{len(self.mesh_of_instance)} instances but {len(M)} transforms")
+        self._commit(M)
+        self.transforms = M      # (only now: a commit that raised leaves the object with the placements the native scene has)
+
+    def _commit(self, M):
+        hops.scene_commit(self._handle, [m.as_wrapper._inner for m in self.meshes], self.mesh_of_instance, M, self.device.index)
+
+    def commit(self):
+        """Read the members' acceleration structures again and upload the scene's table.  Needed after a member's
+        update_raw (or anything else that moves its arrays: include/triro_scene.h); a member's refit needs none."""
+        self._commit(self.transforms)
+
+    def info(self) -> dict:
+        return hops.scene_info(self._handle)
+
+    # -- queries -----------------------------------------------------------------------------
+    def _rays(self, origins, directions, tmin, tmax):
+        return self._helper._range_rays(origins, directions, tmin, tmax)
+
+    def intersects_any(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
+        """Bool[*b]: does the world ray hit any instance at a distance t (P = o + t d) with tmin <= t <= tmax.  The interval
+        is closed, distances are measured from the origin given.  tmin / tmax: None (0 / 1e7), a scalar or anything that
+        broadcasts to [*b]."""
+        o, d, lo, hi = self._rays(origins, directions, tmin, tmax)
+        return hops.scene_any_native(self._handle, self.device.index, o, d, lo, hi)
+
+    def intersects_closest(self, origins, directions, tmin=None, tmax=None):
+        """(hit[*b], front[*b], instance[*b], tri[*b], t[*b], loc[*b,3], uv[*b,2]): the first hit with tmin <= t <= tmax over
+        all instances -- the one that minimises (t, instance, face).  tri is the face index in the member mesh, loc is in
+        world space, uv in object space, front what the placed triangle looks like from the ray.  A miss: False, False,
+        -1, -1, +Inf, 0, 0."""
+        o, d, lo, hi = self._rays(origins, directions, tmin, tmax)
+        return hops.scene_closest_native(self._handle, self.device.index, o, d, lo, hi)
+
+    def segments_any(self, p0, p1) -> torch.Tensor:
+        """Bool[*b]: is the segment from p0 to p1 blocked by any instance: the ray (p0, the float32 p1 - p0) on [0, 1]."""
+        o, d = self._helper._segment_rays(p0, p1)
+        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        return hops.scene_any_native(self._handle, self.device.index, o, d, None, one)
+
+    def segments_closest(self, p0, p1):
+        """The tuple of intersects_closest for the segment from p0 to p1; t is the fraction along it."""
+        o, d = self._helper._segment_rays(p0, p1)
+        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        return hops.scene_closest_native(self._handle, self.device.index, o, d, None, one)
