@@ -146,17 +146,51 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
             if (have && vkeys[owner] == key) vslots[owner] = res.best_slot;   // faces are distinct: one winner
         }
     };
+    // DESCENT PHASE (plain stack): the tree is tens of levels deep and its leaves sit near the bottom, so the first leaf of a
+    // wave shows up late (headline: after 22 of a wave's 48 trips, profiles/r11_descent_model.txt).  Until some lane has
+    // accepted a leaf child every FIFO of the wave is empty and nothing is parked, and a trip of either flavour comes down to
+    // fetch, box test, push / descend / pop: tr_descent_step, without the FIFO's selects, room / has_node, the wave-any test in
+    // front of the leaf block, the drain and tr_done.  No node is skipped and nothing is reordered: every lane visits the nodes
+    // it visits in the loop below, trip by trip, and the state handed over is the state that loop would have reached.  The
+    // trip on which a lane accepts a leaf is not repeated: its leaves go into the empty FIFOs as either flavour would enter
+    // them, and the loop below continues WHERE THE SCHEDULE STANDS -- a trip without the leaf block first when the phase ends
+    // on an odd trip, then at pair `k0` of a round of trips, so that every look at the wave comes at the trip it came at
+    // before.  The phase ends before the first look that could give anything away (trip >= steal_min): the looks it runs past
+    // would have found a busy lane and nothing to do.
+    uint32_t k0 = 0;           // the trips of the loop's first round that are over already (PLAIN: 0, 2 or all 4)
+    if constexpr (PLAIN) {
+        bool l0 = false, l1 = false;       // child 0 / 1 of the lane's last visit is an accepted leaf
+        int32_t c0 = 0, c1 = 0;
+        while (trip < steal_min) {
+            l0 = false; l1 = false;
+            if (fs.node >= 0) tr_descent_step<Q, STATS, COMPACT>(b, r, fs, res, cnt, ring, l0, l1, c0, c1);
+            TR_CONVERGE();
+            trip++;
+            if (TR_WAVE_ANY(l0 || l1) || !TR_WAVE_ANY(fs.node >= 0)) break;
+        }
+        // the last trip's leaves, into FIFOs that are empty (no lane has any unless that trip found the wave's first)
+        fs.p0 = l0 ? ~c0 : (l1 ? ~c1 : -1);
+        fs.p1 = (l0 && l1) ? ~c1 : -1;
+        if (trip & 1u) {
+            trip_step(std::false_type{});
+            TR_CONVERGE();
+            trip++;
+        }
+        k0 = trip == 0u ? 0u : ((trip - 1u) & TR_STEAL_EVERY) + 1u;
+        trip -= k0;
+    }
     for (;;) {
         // TR_STEAL_EVERY+1 plain trips (idle lanes sit them out under the exec mask: a trip takes
         // longer the more lanes take part in its loads), in pairs of a trip with the leaf block and one
         // without (tr_fused_step<..., TEST>), then one look at the wave
 #pragma unroll 1
-        for (uint32_t k = 0; k <= TR_STEAL_EVERY; k += 2) {
+        for (uint32_t k = k0; k <= TR_STEAL_EVERY; k += 2) {
             trip_step(std::true_type{});
             TR_CONVERGE();
             trip_step(std::false_type{});
             TR_CONVERGE();
         }
+        k0 = 0;
         trip += (TR_STEAL_EVERY / 2u + 1u) * 2u;
         if (split) {
             // Rays that are traversed by several lanes share what they have found: a lane's bound is

@@ -1087,6 +1087,40 @@ TR_HD void tr_fused_step(const tr_bvh_view& b, const tr_ray& r, tr_state_t<W>& s
     }
 }
 
+// DESCENT STEP: a trip of a lane whose leaf FIFO is empty and which has nothing parked (p0 = p1 = p2 = pe = -1), for the
+// plain stack by LDS byte address over the grid nodes.  With an empty FIFO both flavours of tr_fused_step do the same: no leaf
+// block, no drain, the node is visited, and the FIFO afterwards holds exactly the accepted leaf children.  This is that trip
+// with everything left out whose result is known: room / has_node, the FIFO's selects, the wave-any tests, the drain.  The
+// caller (wave_traverse_steal) runs it for lanes with st.node >= 0 while NO lane of the wave holds a leaf, and enters the
+// reported leaves -- l0 / l1: child 0 / 1 is an accepted leaf, c0 / c1 the children -- into the FIFO itself, on the one
+// trip that finds some: p0 = the first of them, p1 = the second.  Same fetch, same box test, same cull limit, and the
+// statements of tr_fused_body's tr_plaina_w branch in their order (the descend select first, the pop behind it: part R9).
+// (The report as two registers -- the accepted child or 0, negative = a leaf -- makes the loop eleven scalar instructions
+// shorter and the allocator keep kernel-lifetime values in scratch in the DEEP instantiations: part R11, not this form.)
+template <int Q, bool STATS, bool COMPACT>
+TR_HD void tr_descent_step(const tr_bvh_view& b, const tr_ray& r, tr_astate& st, const tr_result& res, tr_counters* cnt,
+                           const tr_ring ring, bool& l0, bool& l1, int32_t& c0, int32_t& c1) {
+    const tr_i4* np = tr_qnode_ptr<COMPACT>(b, st.node);
+    const tr_rec_q rec = {np[0], np[1]};
+    if (STATS) cnt->nodes++;
+    float tn0, tf0, tn1, tf1;
+    tr_rec_slabs(b, r, rec, tn0, tf0, tn1, tf1);
+    tr_rec_children(rec, c0, c1);
+    const float lim = tr_cull_limit<Q>(res);
+    bool h0 = tr_slab_hit(tn0, tf0, lim);
+    bool h1 = tr_slab_hit(tn1, tf1, lim);
+    l0 = h0 && c0 < 0;
+    l1 = h1 && c1 < 0;
+    h0 = h0 && c0 >= 0;
+    h1 = h1 && c1 >= 0;
+    const tr_aring ar = tr_aring_of(ring);
+    const bool both = h0 && h1;
+    const bool swap = (both && tn1 < tn0) || !h0;   // descend into c1?
+    if (both) tr_addr_push(ar, st.sa, swap ? c0 : c1);
+    st.node = swap ? c1 : c0;
+    if (!(h0 || h1)) st.node = tr_addr_pop(ar, st.sa);
+}
+
 
 // ---- unordered two-phase schedule (any / count / location) --------------------------------------
 // Queries that do not prune by distance gain nothing from near-first order or from testing a
