@@ -949,3 +949,132 @@ def scene_closest_native(handle, device_index, origins, dirs, tmin=None, tmax=No
         _check(lib.tr_scene_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), inst.data_ptr(), tri.data_ptr(), ptr(t),
                                     ptr(hit), ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
     return hit, front, inst, tri, t, loc, uv
+
+
+# --- the faces within a distance of each point (include/triro_within.h, csrc/within.hip) -------------------------------
+_WITHIN_LIB_NAME = "libtriro_within.so"
+WITHIN_ABI_VERSION = 1    # TR_WITHIN_ABI_VERSION of include/triro_within.h
+_within_module = None
+_f32 = C.c_float
+
+# every symbol include/triro_within.h declares: (restype, argtypes)
+WITHIN_ABI = {
+    "tr_within_abi_version": (_int, []),
+    "tr_within_stack_capacity": (_int, []),
+    "tr_within_any": (_int, [_vp, _vp, _i64, _vp, _f32, _vp, _int, _vp]),
+    "tr_within_count": (_int, [_vp, _vp, _i64, _vp, _f32, _vp, _int, _vp]),
+    "tr_within_fill": (_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp]),
+    "tr_within_closest": (_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+def within_library_path() -> str:
+    return os.environ.get("TRIRO_WITHIN_LIBRARY") or os.path.join(os.path.dirname(library_path()), _WITHIN_LIB_NAME)
+
+
+def get_within_module():
+    """libtriro_within.so.  Raises when it is not built or does not match this binding."""
+    global _within_module
+    if _within_module is None:
+        get_module()                       # libtriro_hip.so first: the within library links against it
+        path = within_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in WITHIN_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_within_abi_version() != WITHIN_ABI_VERSION:
+            raise RuntimeError(f"libtriro_within.so ABI version {lib.tr_within_abi_version()} != {WITHIN_ABI_VERSION} expected by this binding")
+        _within_module = lib
+    return _within_module
+
+
+def _within_args(accel_structure, points, radius):
+    """(handle, contiguous points, n, device, radius pointer or None, scalar radius, the radius tensor kept alive)"""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
+            points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    dev, n = points.device, points.shape[0]
+    handle = _handle(accel_structure, points)
+    if isinstance(radius, torch.Tensor):
+        if not radius.is_cuda or radius.device != dev or radius.dtype != torch.float32 or tuple(radius.shape) != (n,) or \
+                not radius.is_contiguous():
+            raise ValueError(f"radius must be a number or a contiguous float32 tensor of {n} elements on the points' device")
+        return handle, points.contiguous(), n, dev, radius.data_ptr(), 0.0, radius
+    r = C.c_float(float(radius)).value      # rounded to float32 (beyond its range: +Inf, as a float32 tensor would hold it)
+    return handle, points.contiguous(), n, dev, None, r, None
+
+
+def within_native(accel_structure, points, radius, query="any", stack_entries=0) -> torch.Tensor:
+    """tr_within_any (query="any": bool[n]) / tr_within_count (query="count": int32[n]) for float32 points [n, 3] on the
+    handle's GPU.  radius: a number, or a dense float32 [n] tensor on that GPU.  stack_entries: 0 = the whole stack,
+    1 .. capacity for tests (same results).  Nothing is allocated by the library and nothing is synchronised."""
+    if query not in ("any", "count"):
+        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
+    lib = get_within_module()
+    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
+    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    with torch.cuda.device(dev):
+        fn = lib.tr_within_any if query == "any" else lib.tr_within_count
+        _check(fn(handle, points.data_ptr(), n, rptr, r, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def within_fill_native(accel_structure, points, radius, count, offsets, total, want_distance=False, want_closest=False,
+                       stack_entries=0):
+    """tr_within_fill: (face int32[total], distance float32[total] or None, closest float32[total, 3] or None), the faces of
+    point i ascending at rows offsets[i] .. offsets[i] + count[i].  count int32[n] is within_native(..., "count") and
+    offsets int64[n] its exclusive scan (tr_hits_scan) for the same points and radii; total (a Python int) sizes the
+    outputs.  Nothing is allocated by the library and nothing is synchronised."""
+    lib = get_within_module()
+    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the points' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    face = _new_output((total,), torch.int32, dev)
+    distance = _new_output((total,), torch.float32, dev) if want_distance else None
+    closest = _new_output((total, 3), torch.float32, dev) if want_closest else None
+    slot = _new_output((total,), torch.int32, dev) if (want_distance or want_closest) and total > 0 else None
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_within_fill(handle, points.data_ptr(), n, rptr, r, count.data_ptr(), offsets.data_ptr(), total, ptr(face),
+                                  ptr(distance), ptr(closest), ptr(slot), int(stack_entries), _stream_ptr(dev)))
+    return face, distance, closest
+
+
+def faces_within_native(accel_structure, points, radius, want_distance=False, want_closest=False, stack_entries=0):
+    """(offsets int64[n + 1], face, distance or None, closest or None): one count launch, one scan, one host read of the
+    total to size the outputs (as intersects_location), one fill."""
+    handle, points, n, dev, rptr, r, keep = _within_args(accel_structure, points, radius)
+    radius = keep if keep is not None else r
+    count = within_native(accel_structure, points, radius, "count", stack_entries)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    face, distance, closest = within_fill_native(accel_structure, points, radius, count, offsets[:n], int(total.value),
+                                                 want_distance, want_closest, stack_entries)
+    return offsets, face, distance, closest
+
+
+def within_closest_native(accel_structure, points, radius, stack_entries=0, want_closest=True, want_distance=True):
+    """tr_within_closest: closest_point_native bounded by the radius -- (closest float32[n, 3] or None, distance float32[n]
+    or None, tri int32[n]), (NaN, +Inf, -1) where no face is within.  radius as for within_native."""
+    lib = get_within_module()
+    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
+    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
+    distance = _new_output((n,), torch.float32, dev) if want_distance else None
+    tri = _new_output((n,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_within_closest(handle, points.data_ptr(), n, rptr, r, closest.data_ptr() if closest is not None else None,
+                                     distance.data_ptr() if distance is not None else None, tri.data_ptr(),
+                                     int(stack_entries), _stream_ptr(dev)))
+    return closest, distance, tri

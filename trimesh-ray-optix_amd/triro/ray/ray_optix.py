@@ -284,13 +284,9 @@ class RayMeshIntersector:
         return contains
 
     # -- proximity (trimesh.proximity; not in the reference) ----------------------------------
-    def closest_point(self, points) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """trimesh.proximity.closest_point: (closest[*b,3] float32, distance[*b] float32, triangle_id[*b] int32) of
-        points [*b, 3], one launch of libtriro_nearest.so (tr_closest_point).  Distances are evaluated in float64 from
-        the float32 inputs; among triangles at exactly the same distance the smaller face index wins (trimesh leaves
-        that open).  A triangle with a NaN or an infinite coordinate is inactive: never returned, as no ray hits it.  A point
-        with a non-finite component, an empty mesh or one without an active triangle: (NaN, +Inf, -1).  Points are converted to
-        contiguous float32 on the acceleration structure's GPU; a tensor on another GPU raises."""
+    def _proximity_points(self, points):
+        """points [*b, 3] as the native proximity entries take them: (flat float32 [n, 3] on the acceleration structure's GPU,
+        the batch shape)"""
         dev = self.mesh_vertices.device
         if isinstance(points, torch.Tensor):
             if not points.is_cuda:
@@ -301,9 +297,65 @@ class RayMeshIntersector:
         p = _to_device_tensor(points, torch.float32, dev)
         if p.dim() < 1 or p.shape[-1] != 3:
             raise ValueError(f"points must have shape [*b, 3], got {tuple(p.shape)}")
-        b = p.shape[:-1]
-        closest, distance, tri = hops.closest_point_native(self.as_wrapper, p.reshape(-1, 3))
+        return p.reshape(-1, 3), p.shape[:-1]
+
+    def _proximity_radius(self, radius, b, name="radius"):
+        """a radius as the native entries take it: a Python float, or -- for anything that is not a single number -- a dense
+        float32 [n] tensor on the acceleration structure's GPU, broadcast to the batch shape `b`"""
+        dev = self.mesh_vertices.device
+        if isinstance(radius, (int, float)):
+            return float(radius)
+        if isinstance(radius, torch.Tensor) and radius.is_cuda and radius.device != dev:
+            raise ValueError(f"{name} is on {radius.device} but the acceleration structure lives on {dev}; "
+                             f"move it or build the intersector on that device")
+        r = _to_device_tensor(radius, torch.float32, dev)
+        try:
+            r = torch.broadcast_to(r, tuple(b))
+        except RuntimeError:
+            raise ValueError(f"{name} of shape {tuple(r.shape)} does not broadcast to the batch shape {tuple(b)}") from None
+        return r.reshape(-1).contiguous()
+
+    def closest_point(self, points, max_distance=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """trimesh.proximity.closest_point: (closest[*b,3] float32, distance[*b] float32, triangle_id[*b] int32) of
+        points [*b, 3], one launch of libtriro_nearest.so (tr_closest_point).  Distances are evaluated in float64 from
+        the float32 inputs; among triangles at exactly the same distance the smaller face index wins (trimesh leaves
+        that open).  A triangle with a NaN or an infinite coordinate is inactive: never returned, as no ray hits it.  A point
+        with a non-finite component, an empty mesh or one without an active triangle: (NaN, +Inf, -1).  Points are converted to
+        contiguous float32 on the acceleration structure's GPU; a tensor on another GPU raises.
+
+        max_distance (a number or a tensor that broadcasts to the batch shape; None: unbounded, the launch above): the
+        nearest triangle within that distance or none -- one launch of libtriro_within.so (tr_within_closest) whose
+        search is bounded from the first node.  A triangle at exactly max_distance is within; a point without one, and a
+        NaN or negative max_distance, answer (NaN, +Inf, -1).  Where the unbounded answer's float64 squared distance
+        is <= max_distance^2 the bounded answer is that answer bit for bit."""
+        flat, b = self._proximity_points(points)
+        if max_distance is None:
+            closest, distance, tri = hops.closest_point_native(self.as_wrapper, flat)
+        else:
+            closest, distance, tri = hops.within_closest_native(self.as_wrapper, flat, self._proximity_radius(max_distance, b, "max_distance"))
         return closest.reshape(*b, 3), distance.reshape(b), tri.reshape(b)
+
+    def within_any(self, points, radius) -> torch.Tensor:
+        """bool[*b]: is any triangle within `radius` of each of points [*b, 3] -- one launch of libtriro_within.so
+        (tr_within_any), the proximity analogue of intersects_any.  "Within" is float64 squared distance (closest_point's)
+        <= radius^2, not strict.  radius: a number or a tensor that broadcasts to the batch shape; NaN or negative: False."""
+        flat, b = self._proximity_points(points)
+        return hops.within_native(self.as_wrapper, flat, self._proximity_radius(radius, b), "any").reshape(b)
+
+    def within_count(self, points, radius) -> torch.Tensor:
+        """int32[*b]: how many triangles are within `radius` of each point (tr_within_count); see within_any"""
+        flat, b = self._proximity_points(points)
+        return hops.within_native(self.as_wrapper, flat, self._proximity_radius(radius, b), "count").reshape(b)
+
+    def faces_within(self, points, radius, return_distance=False, return_closest=False):
+        """trimesh.proximity.nearby_faces with an exact radius: (offsets int64[n + 1], tri_idx int32[h][, distance float32[h]]
+        [, closest float32[h, 3]]) for the points flattened in order -- the triangles within `radius` of point i are
+        tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped; distance and closest are closest_point's values for that
+        (point, triangle).  One count launch, one scan, one host read of the total to size the outputs, one fill."""
+        flat, b = self._proximity_points(points)
+        offsets, face, distance, closest = hops.faces_within_native(self.as_wrapper, flat, self._proximity_radius(radius, b),
+                                                                    return_distance, return_closest)
+        return (offsets, face) + ((distance,) if return_distance else ()) + ((closest,) if return_closest else ())
 
     def signed_distance(self, points, check_direction: Optional[torch.Tensor] = None) -> torch.Tensor:
         """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
