@@ -1078,3 +1078,107 @@ def within_closest_native(accel_structure, points, radius, stack_entries=0, want
                                      distance.data_ptr() if distance is not None else None, tri.data_ptr(),
                                      int(stack_entries), _stream_ptr(dev)))
     return closest, distance, tri
+
+
+# --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
+_CROSS_LIB_NAME = "libtriro_cross.so"
+CROSS_ABI_VERSION = 1    # TR_CROSS_ABI_VERSION of include/triro_cross.h
+_cross_module = None
+
+# every symbol include/triro_cross.h declares: (restype, argtypes)
+CROSS_ABI = {
+    "tr_cross_abi_version": (_int, []),
+    "tr_cross_stack_capacity": (_int, []),
+    "tr_cross_count": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _int, _vp]),
+    "tr_cross_fill": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _int, _vp]),
+}
+
+
+def cross_library_path() -> str:
+    return os.environ.get("TRIRO_CROSS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _CROSS_LIB_NAME)
+
+
+def get_cross_module():
+    """libtriro_cross.so.  Raises when it is not built or does not match this binding."""
+    global _cross_module
+    if _cross_module is None:
+        get_module()                       # libtriro_hip.so first: the cross library links against it
+        path = cross_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in CROSS_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_cross_abi_version() != CROSS_ABI_VERSION:
+            raise RuntimeError(f"libtriro_cross.so ABI version {lib.tr_cross_abi_version()} != {CROSS_ABI_VERSION} expected by this binding")
+        _cross_module = lib
+    return _cross_module
+
+
+def cross_count_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
+    """tr_cross_count: int32[*b], how many triangles each ray crosses within [tmin, tmax] (closed, measured from the origin
+    given, no anchoring), uncapped.  Rays as for intersects_any (any strides); tmin / tmax: None or dense float32 [n], n =
+    the number of rays.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated by
+    the library and nothing is synchronised."""
+    check_rays(origins, dirs)
+    lib = get_cross_module()
+    dev, n = origins.device, origins.numel() // 3
+    handle = _handle(accel_structure, origins)
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    out = _new_output(origins.shape[:-1], torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_cross_count(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
+                                  tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets, total, want_front=False, want_loc=False,
+                      want_uv=False, want_ray=False, ray_base: int = 0, stack_entries=0):
+    """tr_cross_fill: (face int32[total], t float32[total], front bool[total] or None, loc float32[total, 3] or None,
+    uv float32[total, 2] or None, ray int64[total] or None): the crossings of ray i by (t, face) ascending at rows offsets[i]
+    .. offsets[i] + count[i].  count int32[n] is cross_count_native's (flattened) and offsets int64[n] its exclusive scan
+    (tr_hits_scan) for the same rays and bounds; total (a Python int) sizes the outputs.  Nothing is allocated by the library
+    and nothing is synchronised."""
+    check_rays(origins, dirs)
+    lib = get_cross_module()
+    dev, n = origins.device, origins.numel() // 3
+    handle = _handle(accel_structure, origins)
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the rays' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    face = _new_output((total,), torch.int32, dev)
+    t = _new_output((total,), torch.float32, dev)
+    front = _new_output((total,), torch.bool, dev) if want_front else None
+    loc = _new_output((total, 3), torch.float32, dev) if want_loc else None
+    uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
+    ray = _new_output((total,), torch.int64, dev) if want_ray else None
+    slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_cross_fill(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), count.data_ptr(), offsets.data_ptr(), total,
+                                 ptr(face), ptr(t), ptr(front), ptr(loc), ptr(uv), ptr(ray), int(ray_base), ptr(slot), int(stack_entries),
+                                 _stream_ptr(dev)))
+    return face, t, front, loc, uv, ray
+
+
+def cross_all_native(accel_structure, origins, dirs, tmin=None, tmax=None, want_front=False, want_loc=False, want_uv=False,
+                     want_ray=False, ray_base: int = 0, stack_entries=0):
+    """(offsets int64[n + 1], face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened in order:
+    one count launch, one scan, one host read of the total to size the outputs (as faces_within_native), one fill."""
+    n, dev = origins.numel() // 3, origins.device
+    count = cross_count_native(accel_structure, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    return (offsets,) + cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value), want_front,
+                                          want_loc, want_uv, want_ray, ray_base, stack_entries)

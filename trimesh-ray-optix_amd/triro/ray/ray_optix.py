@@ -447,6 +447,42 @@ class RayMeshIntersector:
         one = torch.ones(n, dtype=torch.float32, device=o.device)
         return hops.range_closest_native(self.as_wrapper, o, d, None, one)
 
+    # -- every crossing within a range (trimesh.ray.intersects_location without a cap; an any-hit program with tmin / tmax) --
+    def intersects_count_range(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
+        """int32[*b]: how many triangles each ray crosses at a distance t with tmin <= t <= tmax, uncapped -- one launch of
+        libtriro_cross.so (tr_cross_count).  The interval, its ends and the rays are those of intersects_any_range: closed,
+        measured from the origin given, never anchored; a ray through a shared edge or vertex crosses one owner."""
+        o, d, lo, hi = self._range_rays(origins, directions, tmin, tmax)
+        return hops.cross_count_native(self.as_wrapper, o, d, lo, hi)
+
+    def intersects_all_range(self, origins, directions, tmin=None, tmax=None, return_front=False, return_locations=False,
+                             return_uv=False):
+        """(offsets int64[n + 1], tri_idx int32[h], t float32[h][, front bool[h]][, loc float32[h, 3]][, uv float32[h, 2]])
+        for the rays flattened in order: EVERY crossing of ray i with tmin <= t <= tmax is a row of offsets[i]:offsets[i + 1],
+        ordered by (t, triangle index) ascending, uncapped; front, loc and uv are intersects_closest_range's values for that
+        (ray, triangle), and the first row of a ray is its answer.  One count launch, one scan, one host read of the total
+        to size the outputs, one fill (two launches): the shape of faces_within."""
+        o, d, lo, hi = self._range_rays(origins, directions, tmin, tmax)
+        offsets, face, t, front, loc, uv, _ = hops.cross_all_native(self.as_wrapper, o, d, lo, hi, return_front, return_locations, return_uv)
+        return (offsets, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+
+    def segments_count(self, p0, p1) -> torch.Tensor:
+        """int32[*b]: how many triangles the segment from p0 to p1 crosses.  The ray (p0, the float32 p1 - p0) on the closed
+        interval [0, 1], as segments_any."""
+        o, d = self._segment_rays(p0, p1)
+        n = o.numel() // 3
+        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        return hops.cross_count_native(self.as_wrapper, o, d, None, one)
+
+    def segments_all(self, p0, p1, return_front=False, return_locations=False, return_uv=False):
+        """intersects_all_range for the segments from p0 to p1: the ray (p0, the float32 p1 - p0) on the closed interval
+        [0, 1]; t is the fraction along the segment."""
+        o, d = self._segment_rays(p0, p1)
+        n = o.numel() // 3
+        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        offsets, face, t, front, loc, uv, _ = hops.cross_all_native(self.as_wrapper, o, d, None, one, return_front, return_locations, return_uv)
+        return (offsets, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+
     # -- extras (not in the reference) -------------------------------------------------------
     def bvh_info(self) -> dict:
         return self.as_wrapper.info()
