@@ -20,6 +20,7 @@
 
 #include "tr_internal.h"
 #include "tr_scene.h"
+#include "tr_scene_handle.h"      // struct tr_scene and scene_stale
 #include "../../include/triro_scene.h"
 
 namespace {
@@ -95,18 +96,6 @@ __global__ __launch_bounds__(SC_BS) void k_scene_query(const tr_scene_member* __
                          out.t ? out.t + i : nullptr, out.loc ? out.loc + 3 * i : nullptr, out.uv ? out.uv + 2 * i : nullptr);
 }
 
-// the opaque handle ---------------------------------------------------------------------
-struct tr_scene {
-    int device = 0;
-    void* table = nullptr;          // one hipMalloc: members | instances (grown only)
-    size_t table_bytes = 0;
-    std::vector<const tr_bvh*> members;          // the handles, as given to the last commit
-    std::vector<tr_scene_member> committed;      // ... and their arrays and counts as they were then (the stale check)
-    int64_t ninst = 0, nvalid = 0, commits = 0;
-    const tr_scene_member* d_members = nullptr;
-    const tr_scene_inst* d_insts = nullptr;
-};
-
 namespace {
 
 // tr_rays -> RayFetch: the checks and the stride classes of the other entries.  A COPY of range_fetch (range.hip), kept in
@@ -153,17 +142,6 @@ tr_scene_member member_of(const tr_bvh* b) {
     tr_scene_member m;
     m.nodes = b->nodes; m.links = b->links; m.tris = b->tris; m.num_tris = b->num_tris;
     return m;
-}
-
-// has any member's arrays, count or device changed since the commit?  (host only: reads the handles)
-bool scene_stale(const tr_scene* s) {
-    for (size_t k = 0; k < s->members.size(); k++) {
-        const tr_bvh* b = s->members[k];
-        const tr_scene_member& c = s->committed[k];
-        if (b->device != s->device || b->nodes != c.nodes || b->links != c.links || b->tris != c.tris || b->num_tris != c.num_tris)
-            return true;
-    }
-    return false;
 }
 
 template <int Q>

@@ -1182,3 +1182,105 @@ def cross_all_native(accel_structure, origins, dirs, tmin=None, tmax=None, want_
                                          C.byref(total), _stream_ptr(dev)))
     return (offsets,) + cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value), want_front,
                                           want_loc, want_uv, want_ray, ray_base, stack_entries)
+
+
+# --- every crossing of a world ray over an instanced scene (include/triro_scene_cross.h, csrc/scene_cross.hip) ------------
+_SCENE_CROSS_LIB_NAME = "libtriro_scene_cross.so"
+SCENE_CROSS_ABI_VERSION = 1    # TR_SCENE_CROSS_ABI_VERSION of include/triro_scene_cross.h
+_scene_cross_module = None
+
+# every symbol include/triro_scene_cross.h declares: (restype, argtypes)
+SCENE_CROSS_ABI = {
+    "tr_scene_cross_abi_version": (_int, []),
+    "tr_scene_cross_stack_capacity": (_int, []),
+    "tr_scene_cross_count": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _int, _vp]),
+    "tr_scene_cross_fill": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _int, _vp]),
+}
+
+
+def scene_cross_library_path() -> str:
+    return os.environ.get("TRIRO_SCENE_CROSS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_CROSS_LIB_NAME)
+
+
+def get_scene_cross_module():
+    """libtriro_scene_cross.so.  Raises when it is not built or does not match this binding."""
+    global _scene_cross_module
+    if _scene_cross_module is None:
+        get_scene_module()                 # libtriro_hip.so and libtriro_scene.so first: the handles are theirs
+        path = scene_cross_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in SCENE_CROSS_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_scene_cross_abi_version() != SCENE_CROSS_ABI_VERSION:
+            raise RuntimeError(f"libtriro_scene_cross.so ABI version {lib.tr_scene_cross_abi_version()} != {SCENE_CROSS_ABI_VERSION} "
+                               f"expected by this binding")
+        _scene_cross_module = lib
+    return _scene_cross_module
+
+
+def scene_cross_count_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
+    """tr_scene_cross_count: int32[*b], how many (instance, triangle) pairs each world ray crosses within [tmin, tmax],
+    uncapped.  Arguments as scene_any_native.  Nothing is allocated by the library and nothing is synchronised."""
+    _scene_rays(origins, dirs, device_index)
+    lib = get_scene_cross_module()
+    dev, n = origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    out = _new_output(origins.shape[:-1], torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_cross_count(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
+                                        tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets, total, want_front=False, want_loc=False,
+                            want_uv=False, want_ray=False, ray_base: int = 0, stack_entries=0):
+    """tr_scene_cross_fill: (instance int32[total], face int32[total], t float32[total], front bool[total] or None,
+    loc float32[total, 3] or None, uv float32[total, 2] or None, ray int64[total] or None): the crossings of ray i by
+    (t, instance, face) ascending at rows offsets[i] .. offsets[i] + count[i].  count int32[n] is scene_cross_count_native's
+    (flattened) and offsets int64[n] its exclusive scan (tr_hits_scan) for the same rays and bounds; total (a Python int)
+    sizes the outputs.  Nothing is allocated by the library and nothing is synchronised."""
+    _scene_rays(origins, dirs, device_index)
+    lib = get_scene_cross_module()
+    dev, n = origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the rays' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    inst = _new_output((total,), torch.int32, dev)
+    face = _new_output((total,), torch.int32, dev)
+    t = _new_output((total,), torch.float32, dev)
+    front = _new_output((total,), torch.bool, dev) if want_front else None
+    loc = _new_output((total, 3), torch.float32, dev) if want_loc else None
+    uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
+    ray = _new_output((total,), torch.int64, dev) if want_ray else None
+    slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_cross_fill(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), count.data_ptr(), offsets.data_ptr(),
+                                       total, ptr(inst), ptr(face), ptr(t), ptr(front), ptr(loc), ptr(uv), ptr(ray), int(ray_base), ptr(slot),
+                                       int(stack_entries), _stream_ptr(dev)))
+    return inst, face, t, front, loc, uv, ray
+
+
+def scene_cross_all_native(handle, device_index, origins, dirs, tmin=None, tmax=None, want_front=False, want_loc=False, want_uv=False,
+                           want_ray=False, ray_base: int = 0, stack_entries=0):
+    """(offsets int64[n + 1], instance, face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened
+    in order: one count launch, one scan, one host read of the total to size the outputs, one fill: as cross_all_native."""
+    n, dev = origins.numel() // 3, origins.device
+    count = scene_cross_count_native(handle, device_index, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    return (offsets,) + scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value),
+                                                want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)

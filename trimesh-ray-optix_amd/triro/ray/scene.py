@@ -118,3 +118,39 @@ class RaySceneIntersector:
         o, d = self._helper._segment_rays(p0, p1)
         one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
         return hops.scene_closest_native(self._handle, self.device.index, o, d, None, one)
+
+    # -- every crossing within a range (libtriro_scene_cross.so, include/triro_scene_cross.h) ---------------------------
+    def intersects_count(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
+        """int32[*b]: how many (instance, triangle) pairs the world ray crosses at a distance t with tmin <= t <= tmax,
+        uncapped.  The interval, its ends and the rays are those of intersects_any; count > 0 is its answer."""
+        o, d, lo, hi = self._rays(origins, directions, tmin, tmax)
+        return hops.scene_cross_count_native(self._handle, self.device.index, o, d, lo, hi)
+
+    def _all(self, o, d, lo, hi, return_front, return_locations, return_uv):
+        offsets, inst, face, t, front, loc, uv, _ = hops.scene_cross_all_native(self._handle, self.device.index, o, d, lo, hi, return_front,
+                                                                               return_locations, return_uv)
+        return (offsets, inst, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+
+    def intersects_all(self, origins, directions, tmin=None, tmax=None, return_front=False, return_locations=False, return_uv=False):
+        """(offsets int64[n + 1], instance int32[h], tri_idx int32[h], t float32[h][, front bool[h]][, loc float32[h, 3]]
+        [, uv float32[h, 2]]) for the rays flattened in order: EVERY crossing of ray i with tmin <= t <= tmax over all
+        instances is a row of offsets[i]:offsets[i + 1], ordered by (t, instance, triangle index) ascending, uncapped.
+        tri_idx is the face index in the member mesh; front, loc (world space) and uv (object space) are intersects_closest's
+        values for that (ray, instance, triangle), and the first row of a ray is its answer.  One count launch, one scan, one
+        host read of the total to size the outputs, one fill (two launches): RayMeshIntersector.intersects_all_range on a
+        scene."""
+        o, d, lo, hi = self._rays(origins, directions, tmin, tmax)
+        return self._all(o, d, lo, hi, return_front, return_locations, return_uv)
+
+    def segments_count(self, p0, p1) -> torch.Tensor:
+        """int32[*b]: how many (instance, triangle) pairs the segment from p0 to p1 crosses: the ray (p0, the float32
+        p1 - p0) on the closed interval [0, 1], as segments_any."""
+        o, d = self._helper._segment_rays(p0, p1)
+        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        return hops.scene_cross_count_native(self._handle, self.device.index, o, d, None, one)
+
+    def segments_all(self, p0, p1, return_front=False, return_locations=False, return_uv=False):
+        """intersects_all for the segments from p0 to p1; t is the fraction along the segment."""
+        o, d = self._helper._segment_rays(p0, p1)
+        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        return self._all(o, d, None, one, return_front, return_locations, return_uv)
