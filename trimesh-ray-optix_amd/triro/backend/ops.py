@@ -1080,6 +1080,107 @@ def within_closest_native(accel_structure, points, radius, stack_entries=0, want
     return closest, distance, tri
 
 
+# --- the faces that meet each axis-aligned box (include/triro_boxes.h, csrc/boxes.hip) ------------------------------------
+_BOXES_LIB_NAME = "libtriro_boxes.so"
+BOXES_ABI_VERSION = 1    # TR_BOXES_ABI_VERSION of include/triro_boxes.h
+_boxes_module = None
+
+# every symbol include/triro_boxes.h declares: (restype, argtypes)
+BOXES_ABI = {
+    "tr_boxes_abi_version": (_int, []),
+    "tr_boxes_stack_capacity": (_int, []),
+    "tr_boxes_any": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_boxes_count": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_boxes_fill": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
+}
+
+
+def boxes_library_path() -> str:
+    return os.environ.get("TRIRO_BOXES_LIBRARY") or os.path.join(os.path.dirname(library_path()), _BOXES_LIB_NAME)
+
+
+def get_boxes_module():
+    """libtriro_boxes.so.  Raises when it is not built or does not match this binding."""
+    global _boxes_module
+    if _boxes_module is None:
+        get_module()                       # libtriro_hip.so first: the boxes library links against it
+        path = boxes_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in BOXES_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_boxes_abi_version() != BOXES_ABI_VERSION:
+            raise RuntimeError(f"libtriro_boxes.so ABI version {lib.tr_boxes_abi_version()} != {BOXES_ABI_VERSION} expected by this binding")
+        _boxes_module = lib
+    return _boxes_module
+
+
+def _boxes_args(accel_structure, lo, hi):
+    """(handle, contiguous lo, contiguous hi, n, device)"""
+    for name, t in (("lo", lo), ("hi", hi)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
+    if hi.device != lo.device or hi.shape != lo.shape:
+        raise ValueError(f"lo {tuple(lo.shape)} on {lo.device} and hi {tuple(hi.shape)} on {hi.device} must have one shape and one device")
+    return _handle(accel_structure, lo), lo.contiguous(), hi.contiguous(), lo.shape[0], lo.device
+
+
+def boxes_native(accel_structure, lo, hi, query="any", stack_entries=0) -> torch.Tensor:
+    """tr_boxes_any (query="any": bool[n]) / tr_boxes_count (query="count": int32[n]) for the closed boxes [lo, hi], float32
+    [n, 3] each, on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing
+    is allocated by the library and nothing is synchronised."""
+    if query not in ("any", "count"):
+        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
+    lib = get_boxes_module()
+    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
+    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    with torch.cuda.device(dev):
+        fn = lib.tr_boxes_any if query == "any" else lib.tr_boxes_count
+        _check(fn(handle, lo.data_ptr(), hi.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def boxes_fill_native(accel_structure, lo, hi, count, offsets, total, want_inside=False, stack_entries=0):
+    """tr_boxes_fill: (face int32[total], inside bool[total] or None), the faces of box i ascending at rows offsets[i] ..
+    offsets[i] + count[i].  count int32[n] is boxes_native(..., "count") and offsets int64[n] its exclusive scan
+    (tr_hits_scan) for the same boxes; total (a Python int) sizes the outputs.  Nothing is allocated by the library and
+    nothing is synchronised."""
+    lib = get_boxes_module()
+    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the boxes' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    face = _new_output((total,), torch.int32, dev)
+    inside = _new_output((total,), torch.bool, dev) if want_inside else None
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_boxes_fill(handle, lo.data_ptr(), hi.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, ptr(face),
+                                 ptr(inside), int(stack_entries), _stream_ptr(dev)))
+    return face, inside
+
+
+def faces_in_boxes_native(accel_structure, lo, hi, want_inside=False, stack_entries=0):
+    """(offsets int64[n + 1], face, inside or None): one count launch, one scan, one host read of the total to size the
+    outputs (as faces_within_native), one fill."""
+    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
+    count = boxes_native(accel_structure, lo, hi, "count", stack_entries)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    face, inside = boxes_fill_native(accel_structure, lo, hi, count, offsets[:n], int(total.value), want_inside, stack_entries)
+    return offsets, face, inside
+
+
 # --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
 _CROSS_LIB_NAME = "libtriro_cross.so"
 CROSS_ABI_VERSION = 1    # TR_CROSS_ABI_VERSION of include/triro_cross.h

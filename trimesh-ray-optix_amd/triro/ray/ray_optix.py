@@ -357,6 +357,115 @@ class RayMeshIntersector:
                                                                     return_distance, return_closest)
         return (offsets, face) + ((distance,) if return_distance else ()) + ((closest,) if return_closest else ())
 
+    # -- box queries (libtriro_boxes.so, include/triro_boxes.h; not in the reference) ---------
+    def _query_boxes(self, lo, hi):
+        """lo, hi [*b, 3], broadcast against each other, as the native box entries take them: (flat float32 lo [n, 3], flat
+        float32 hi [n, 3], the batch shape).  Conversion and device rules are those of _proximity_points, for each of the two."""
+        dev = self.mesh_vertices.device
+        corners = []
+        for name, x in (("lo", lo), ("hi", hi)):
+            if isinstance(x, torch.Tensor):
+                if not x.is_cuda:
+                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
+                if x.device != dev:
+                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
+                                     f"move it or build the intersector on that device")
+            t = _to_device_tensor(x, torch.float32, dev)
+            if t.dim() < 1 or t.shape[-1] != 3:
+                raise ValueError(f"{name} must have shape [*b, 3], got {tuple(t.shape)}")
+            corners.append(t)
+        try:
+            shape = torch.broadcast_shapes(corners[0].shape, corners[1].shape)
+        except RuntimeError:
+            raise ValueError(f"lo of shape {tuple(corners[0].shape)} and hi of shape {tuple(corners[1].shape)} do not broadcast") from None
+        lo, hi = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in corners)
+        return lo, hi, shape[:-1]
+
+    def boxes_any(self, lo, hi) -> torch.Tensor:
+        """bool[*b]: does any triangle meet the closed axis-aligned box [lo, hi] -- one launch of libtriro_boxes.so
+        (tr_boxes_any).  lo and hi are [*b, 3] and broadcast against each other.  A triangle MEETS a box when they share a
+        point, touching included (csrc/tr_boxes.h has the predicate).  Flat boxes, lines and points are boxes; a box with a NaN,
+        an infinity or lo > hi on some axis meets nothing, and a triangle with a non-finite coordinate is never met."""
+        lo, hi, b = self._query_boxes(lo, hi)
+        return hops.boxes_native(self.as_wrapper, lo, hi, "any").reshape(b)
+
+    def boxes_count(self, lo, hi) -> torch.Tensor:
+        """int32[*b]: how many triangles meet each box (tr_boxes_count); see boxes_any"""
+        lo, hi, b = self._query_boxes(lo, hi)
+        return hops.boxes_native(self.as_wrapper, lo, hi, "count").reshape(b)
+
+    def faces_in_boxes(self, lo, hi, return_inside=False):
+        """(offsets int64[n + 1], tri_idx int32[h][, inside bool[h]]) for the boxes flattened in order -- the triangles that
+        meet box i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped; inside[k] says that all three vertices of
+        that triangle lie in the box.  One count launch, one scan, one host read of the total to size the outputs, one fill."""
+        lo, hi, b = self._query_boxes(lo, hi)
+        offsets, face, inside = hops.faces_in_boxes_native(self.as_wrapper, lo, hi, return_inside)
+        return (offsets, face) + ((inside,) if return_inside else ())
+
+    def surface_voxels(self, pitch, origin=None, chunk=1 << 20) -> torch.Tensor:
+        """int64[m, 3]: the integer cells (i, j, k) of the grid with spacing `pitch` whose closed box meets the surface, in
+        lexicographic order -- surface voxelisation as host code on boxes_any, `chunk` cells per launch.  The planes of axis
+        a are P_a(i) = float32(origin[a] + i * pitch), evaluated in float64; cell (i, j, k) is the box [P(i), P(i + 1)] x
+        [P(j), P(j + 1)] x [P(k), P(k + 1)], so neighbouring cells share a plane exactly and a triangle lying in that plane
+        belongs to both.  The grid covers the box of the active triangles, the cells that only touch it from outside included;
+        origin defaults to its lower corner.  A pitch that is not finite and positive raises, and so does one below the float32
+        resolution of the grid's coordinates (the planes of neighbouring cells would coincide)."""
+        pitch = float(pitch)
+        if not (np.isfinite(pitch) and pitch > 0):
+            raise ValueError(f"pitch must be finite and positive, got {pitch!r}")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be positive")
+        dev = self.mesh_vertices.device
+        empty = torch.zeros((0, 3), dtype=torch.int64, device=dev)
+        tri = self.mesh_vertices[self.mesh_faces.long()] if self.mesh_faces.numel() else self.mesh_vertices.new_zeros((0, 3, 3))
+        tri = tri[torch.isfinite(tri).all(dim=2).all(dim=1)]
+        if tri.shape[0] == 0:
+            return empty
+        lo = tri.amin(dim=(0, 1)).double().cpu().numpy()
+        hi = tri.amax(dim=(0, 1)).double().cpu().numpy()
+        org = lo.copy() if origin is None else np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin, np.float64).reshape(-1)
+        if org.shape != (3,) or not np.isfinite(org).all():
+            raise ValueError("origin must be three finite numbers")
+        fmax = float(np.finfo(np.float32).max)
+        with np.errstate(over="ignore"):
+            resolution = float(np.spacing(np.float32(max(np.abs(lo).max(), np.abs(hi).max(), np.abs(org).max()))))
+        if not pitch >= resolution or ((hi - org) / pitch).max() - ((lo - org) / pitch).min() > 2.0 ** 31:
+            raise ValueError(f"pitch {pitch!r} is below the float32 resolution {resolution!r} of the grid's coordinates, or the grid "
+                             f"has more than 2^31 cells on an axis")
+
+        def plane(a, i):
+            with np.errstate(over="ignore"):
+                return np.clip(np.float32(org[a] + np.float64(i) * pitch), -fmax, fmax)
+
+        first, planes = [], []
+        for a in range(3):
+            # the cells whose interval [P(i), P(i + 1)] reaches [lo, hi]: P is monotone in i, so both ends are found by stepping
+            i0 = int(np.floor((lo[a] - org[a]) / pitch))
+            while plane(a, i0) >= lo[a] and plane(a, i0) > -fmax:
+                i0 -= 1
+            while plane(a, i0 + 1) < lo[a]:
+                i0 += 1
+            i1 = max(i0, int(np.floor((hi[a] - org[a]) / pitch)))
+            while plane(a, i1 + 1) <= hi[a] and plane(a, i1 + 1) < fmax:
+                i1 += 1
+            while i1 > i0 and plane(a, i1) > hi[a]:
+                i1 -= 1
+            first.append(i0)
+            planes.append(torch.from_numpy(np.ascontiguousarray(plane(a, np.arange(i0, i1 + 2)), np.float32)).to(dev))
+        nx, ny, nz = (len(p) - 1 for p in planes)
+        cells = nx * ny * nz
+        base = torch.tensor(first, dtype=torch.int64, device=dev)
+        found = []
+        for start in range(0, cells, chunk):
+            flat = torch.arange(start, min(start + chunk, cells), dtype=torch.int64, device=dev)
+            ijk = torch.stack((flat // (ny * nz), (flat // nz) % ny, flat % nz), dim=1)
+            blo = torch.stack([planes[a][ijk[:, a]] for a in range(3)], dim=1)
+            bhi = torch.stack([planes[a][ijk[:, a] + 1] for a in range(3)], dim=1)
+            met = hops.boxes_native(self.as_wrapper, blo, bhi, "any")
+            found.append(ijk[met] + base)
+        return torch.cat(found) if found else empty
+
     def signed_distance(self, points, check_direction: Optional[torch.Tensor] = None) -> torch.Tensor:
         """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
         POSITIVE inside, negative elsewhere (trimesh's convention).  `check_direction` is contains_points' argument."""
