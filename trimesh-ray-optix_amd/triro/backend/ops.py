@@ -1181,6 +1181,101 @@ def faces_in_boxes_native(accel_structure, lo, hi, want_inside=False, stack_entr
     return offsets, face, inside
 
 
+# --- the faces that meet each query triangle (include/triro_tris.h, csrc/tris.hip) ----------------------------------------
+_TRIS_LIB_NAME = "libtriro_tris.so"
+TRIS_ABI_VERSION = 1    # TR_TRIS_ABI_VERSION of include/triro_tris.h
+_tris_module = None
+
+# every symbol include/triro_tris.h declares: (restype, argtypes)
+TRIS_ABI = {
+    "tr_tris_abi_version": (_int, []),
+    "tr_tris_stack_capacity": (_int, []),
+    "tr_tris_any": (_int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_tris_count": (_int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_tris_fill": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp]),
+}
+
+
+def tris_library_path() -> str:
+    return os.environ.get("TRIRO_TRIS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _TRIS_LIB_NAME)
+
+
+def get_tris_module():
+    """libtriro_tris.so.  Raises when it is not built or does not match this binding."""
+    global _tris_module
+    if _tris_module is None:
+        get_module()                       # libtriro_hip.so first: the triangle library links against it
+        path = tris_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in TRIS_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_tris_abi_version() != TRIS_ABI_VERSION:
+            raise RuntimeError(f"libtriro_tris.so ABI version {lib.tr_tris_abi_version()} != {TRIS_ABI_VERSION} expected by this binding")
+        _tris_module = lib
+    return _tris_module
+
+
+def _tris_args(accel_structure, tri):
+    """(handle, contiguous triangles, n, device)"""
+    if not isinstance(tri, torch.Tensor) or not tri.is_cuda or tri.dtype != torch.float32 or tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3):
+        raise ValueError("triangles must be a float32 GPU tensor of shape [n, 3, 3]")
+    return _handle(accel_structure, tri), tri.contiguous(), tri.shape[0], tri.device
+
+
+def tris_native(accel_structure, tri, query="any", stack_entries=0) -> torch.Tensor:
+    """tr_tris_any (query="any": bool[n]) / tr_tris_count (query="count": int32[n]) for the query triangles, float32 [n, 3, 3],
+    on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated
+    by the library and nothing is synchronised."""
+    if query not in ("any", "count"):
+        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
+    lib = get_tris_module()
+    handle, tri, n, dev = _tris_args(accel_structure, tri)
+    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    with torch.cuda.device(dev):
+        fn = lib.tr_tris_any if query == "any" else lib.tr_tris_count
+        _check(fn(handle, tri.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def tris_fill_native(accel_structure, tri, count, offsets, total, stack_entries=0) -> torch.Tensor:
+    """tr_tris_fill: face int32[total], the faces of query i ascending at rows offsets[i] .. offsets[i] + count[i].  count
+    int32[n] is tris_native(..., "count") and offsets int64[n] its exclusive scan (tr_hits_scan) for the same queries; total (a
+    Python int) sizes the output.  Nothing is allocated by the library and nothing is synchronised."""
+    lib = get_tris_module()
+    handle, tri, n, dev = _tris_args(accel_structure, tri)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the triangles' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    face = _new_output((total,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_tris_fill(handle, tri.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
+                                face.data_ptr() if total else None, int(stack_entries), _stream_ptr(dev)))
+    return face
+
+
+def faces_meeting_triangles_native(accel_structure, tri, stack_entries=0):
+    """(offsets int64[n + 1], face int32[h]): one count launch, one scan, one host read of the total to size the output (as
+    faces_in_boxes_native), one fill."""
+    handle, tri, n, dev = _tris_args(accel_structure, tri)
+    count = tris_native(accel_structure, tri, "count", stack_entries)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    face = tris_fill_native(accel_structure, tri, count, offsets[:n], int(total.value), stack_entries)
+    return offsets, face
+
+
 # --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
 _CROSS_LIB_NAME = "libtriro_cross.so"
 CROSS_ABI_VERSION = 1    # TR_CROSS_ABI_VERSION of include/triro_cross.h

@@ -466,6 +466,88 @@ class RayMeshIntersector:
             found.append(ijk[met] + base)
         return torch.cat(found) if found else empty
 
+    # -- triangle queries (libtriro_tris.so, include/triro_tris.h; not in the reference) ------
+    def _query_triangles(self, triangles):
+        """triangles [*b, 3, 3] as the native triangle entries take them: (flat float32 [n, 3, 3], the batch shape).  Conversion
+        and device rules are those of the box queries."""
+        dev = self.mesh_vertices.device
+        if isinstance(triangles, torch.Tensor):
+            if not triangles.is_cuda:
+                raise ValueError("triangles must reside on a GPU (cuda/HIP) device")
+            if triangles.device != dev:
+                raise ValueError(f"triangles is on {triangles.device} but the acceleration structure lives on {dev}; "
+                                 f"move it or build the intersector on that device")
+        t = _to_device_tensor(triangles, torch.float32, dev)
+        if t.dim() < 2 or tuple(t.shape[-2:]) != (3, 3):
+            raise ValueError(f"triangles must have shape [*b, 3, 3], got {tuple(t.shape)}")
+        return t.reshape(-1, 3, 3).contiguous(), t.shape[:-2]
+
+    def triangles_any(self, triangles) -> torch.Tensor:
+        """bool[*b]: does any face of the mesh meet each of triangles [*b, 3, 3] -- one launch of libtriro_tris.so
+        (tr_tris_any), the narrow phase of mesh against mesh.  Two triangles MEET when both have area and the closed triangles
+        share a point, touching included (csrc/tr_tris.h has the predicate: seventeen separating axes in float64).  A query
+        with a NaN or an infinity, or one without area (a segment, a point), meets nothing; a face with a non-finite
+        coordinate or without area is never met."""
+        flat, b = self._query_triangles(triangles)
+        return hops.tris_native(self.as_wrapper, flat, "any").reshape(b)
+
+    def triangles_count(self, triangles) -> torch.Tensor:
+        """int32[*b]: how many faces meet each triangle (tr_tris_count); see triangles_any"""
+        flat, b = self._query_triangles(triangles)
+        return hops.tris_native(self.as_wrapper, flat, "count").reshape(b)
+
+    def faces_meeting_triangles(self, triangles) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(offsets int64[n + 1], tri_idx int32[h]) for the triangles flattened in order -- the faces that meet triangle i are
+        tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped.  One count launch, one scan, one host read of the total to size
+        the output, one fill."""
+        flat, _ = self._query_triangles(triangles)
+        return hops.faces_meeting_triangles_native(self.as_wrapper, flat)
+
+    def _other_triangles(self, vertices, faces, chunk):
+        """the faces of another mesh as query triangles: float32 [m, 3, 3] on the acceleration structure's GPU (vertices[faces]
+        gathered there), and the checked chunk size"""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be positive")
+        dev = self.mesh_vertices.device
+        for name, x in (("vertices", vertices), ("faces", faces)):
+            if isinstance(x, torch.Tensor) and x.is_cuda and x.device != dev:
+                raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
+                                 f"move it or build the intersector on that device")
+        v = _to_device_tensor(vertices, torch.float32, dev)
+        f = _to_device_tensor(faces, torch.int64, dev)
+        if v.dim() != 2 or v.shape[1] != 3:
+            raise ValueError(f"vertices must have shape [v, 3], got {tuple(v.shape)}")
+        if f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError(f"faces must have shape [m, 3], got {tuple(f.shape)}")
+        if f.numel() and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+            raise ValueError(f"faces index outside the {v.shape[0]} vertices")
+        return v[f].contiguous(), chunk
+
+    def mesh_collides(self, vertices, faces, chunk=1 << 20) -> bool:
+        """does any face of the other mesh (vertices [v, 3], faces [m, 3]) meet any face of this one (triangles_any's
+        predicate: touching counts, faces without area never meet)?  Host code on triangles_any, `chunk` faces per launch;
+        stops at the first chunk that says yes."""
+        tri, chunk = self._other_triangles(vertices, faces, chunk)
+        for start in range(0, tri.shape[0], chunk):
+            if bool(hops.tris_native(self.as_wrapper, tri[start:start + chunk], "any").any()):
+                return True
+        return False
+
+    def mesh_contacts(self, vertices, faces, chunk=1 << 20) -> torch.Tensor:
+        """int64[m, 2]: every pair (face of the other mesh, face of this mesh) that meets, in lexicographic order -- the contact
+        pairs of two meshes.  Host code on faces_meeting_triangles, `chunk` faces of the other mesh per count / scan / fill;
+        the result does not depend on `chunk`."""
+        tri, chunk = self._other_triangles(vertices, faces, chunk)
+        dev = self.mesh_vertices.device
+        found = []
+        for start in range(0, tri.shape[0], chunk):
+            offsets, own = hops.faces_meeting_triangles_native(self.as_wrapper, tri[start:start + chunk])
+            rows = torch.arange(own.shape[0], dtype=torch.int64, device=dev)
+            other = torch.searchsorted(offsets[1:].contiguous(), rows, right=True) + start      # the query each row belongs to
+            found.append(torch.stack((other, own.long()), dim=1))
+        return torch.cat(found) if found else torch.zeros((0, 2), dtype=torch.int64, device=dev)
+
     def signed_distance(self, points, check_direction: Optional[torch.Tensor] = None) -> torch.Tensor:
         """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
         POSITIVE inside, negative elsewhere (trimesh's convention).  `check_direction` is contains_points' argument."""
