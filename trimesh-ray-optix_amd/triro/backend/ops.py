@@ -1480,3 +1480,110 @@ def scene_cross_all_native(handle, device_index, origins, dirs, tmin=None, tmax=
                                          C.byref(total), _stream_ptr(dev)))
     return (offsets,) + scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value),
                                                 want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)
+
+
+# --- which instances of a scene hold a point (include/triro_scene_points.h, csrc/scene_points.hip) -------------------------
+_SCENE_POINTS_LIB_NAME = "libtriro_scene_points.so"
+SCENE_POINTS_ABI_VERSION = 1    # TR_SCENE_POINTS_ABI_VERSION of include/triro_scene_points.h
+_scene_points_module = None
+
+# every symbol include/triro_scene_points.h declares: (restype, argtypes)
+SCENE_POINTS_ABI = {
+    "tr_scene_points_abi_version": (_int, []),
+    "tr_scene_points_stack_capacity": (_int, []),
+    "tr_scene_points_any": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp]),
+    "tr_scene_points_count": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp]),
+    "tr_scene_points_fill": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp]),
+}
+
+
+def scene_points_library_path() -> str:
+    return os.environ.get("TRIRO_SCENE_POINTS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_POINTS_LIB_NAME)
+
+
+def get_scene_points_module():
+    """libtriro_scene_points.so.  Raises when it is not built or does not match this binding."""
+    global _scene_points_module
+    if _scene_points_module is None:
+        get_scene_module()                 # libtriro_hip.so and libtriro_scene.so first: the handles are theirs
+        path = scene_points_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in SCENE_POINTS_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_scene_points_abi_version() != SCENE_POINTS_ABI_VERSION:
+            raise RuntimeError(f"libtriro_scene_points.so ABI version {lib.tr_scene_points_abi_version()} != {SCENE_POINTS_ABI_VERSION} "
+                               f"expected by this binding")
+        _scene_points_module = lib
+    return _scene_points_module
+
+
+def _scene_points_args(points, direction, device_index):
+    """(contiguous points, contiguous direction, n, device)"""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    if points.device.index != device_index:
+        raise ValueError(f"points are on {points.device} but the scene lives on cuda:{device_index}; move the points")
+    if not isinstance(direction, torch.Tensor) or direction.device != points.device or direction.dtype != torch.float32 or direction.numel() != 3:
+        raise ValueError("direction must be a float32 tensor of three elements on the points' device")
+    return points.contiguous(), direction.reshape(3).contiguous(), points.shape[0], points.device
+
+
+def scene_points_any_native(handle, device_index, points, direction, stack_entries=0) -> torch.Tensor:
+    """tr_scene_points_any: bool[n], is each of points float32 [n, 3] inside some instance, by the parity of the crossings of
+    (p, direction) and (p, -direction) per instance.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same
+    results).  Nothing is allocated by the library and nothing is synchronised."""
+    lib = get_scene_points_module()
+    points, direction, n, dev = _scene_points_args(points, direction, device_index)
+    out = _new_output((n,), torch.bool, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_points_any(handle, points.data_ptr(), n, direction.data_ptr(), out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def scene_points_count_native(handle, device_index, points, direction, stack_entries=0) -> torch.Tensor:
+    """tr_scene_points_count: int32[n], how many instances each point is inside.  Arguments as scene_points_any_native."""
+    lib = get_scene_points_module()
+    points, direction, n, dev = _scene_points_args(points, direction, device_index)
+    out = _new_output((n,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_points_count(handle, points.data_ptr(), n, direction.data_ptr(), out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return out
+
+
+def scene_points_fill_native(handle, device_index, points, direction, count, offsets, total, stack_entries=0) -> torch.Tensor:
+    """tr_scene_points_fill: instance int32[total], the instances that hold point i ascending at rows offsets[i] ..
+    offsets[i] + count[i].  count int32[n] is scene_points_count_native's and offsets int64[n] its exclusive scan
+    (tr_hits_scan) for the same points and direction; total (a Python int) sizes the output.  Nothing is allocated by the
+    library and nothing is synchronised."""
+    lib = get_scene_points_module()
+    points, direction, n, dev = _scene_points_args(points, direction, device_index)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the points' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    inst = _new_output((total,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_points_fill(handle, points.data_ptr(), n, direction.data_ptr(), count.data_ptr(), offsets.data_ptr(), total,
+                                        inst.data_ptr() if total else None, int(stack_entries), _stream_ptr(dev)))
+    return inst
+
+
+def scene_points_list_native(handle, device_index, points, direction, stack_entries=0):
+    """(offsets int64[n + 1], instance int32[h]): one count launch, one scan, one host read of the total to size the output
+    (as faces_in_boxes_native), one fill."""
+    points, direction, n, dev = _scene_points_args(points, direction, device_index)
+    count = scene_points_count_native(handle, device_index, points, direction, stack_entries)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    return offsets, scene_points_fill_native(handle, device_index, points, direction, count, offsets[:n], int(total.value), stack_entries)

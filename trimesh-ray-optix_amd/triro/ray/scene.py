@@ -154,3 +154,41 @@ class RaySceneIntersector:
         o, d = self._helper._segment_rays(p0, p1)
         one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
         return self._all(o, d, None, one, return_front, return_locations, return_uv)
+
+    # -- which instances hold a point (libtriro_scene_points.so, include/triro_scene_points.h) ------------------------------
+    def _points(self, points, check_direction):
+        """points [*b, 3] and the direction as the native entries take them: (flat float32 [n, 3] on the scene's GPU, float32
+        [3] there, the batch shape).  Conversion and device rules for the points are those of the box queries of
+        RayMeshIntersector; check_direction is None (the reference's default direction) or three numbers."""
+        flat, b = self._helper._proximity_points(points)
+        if check_direction is None:
+            direction = torch.tensor(RayMeshIntersector._DEFAULT_DIRECTION, dtype=torch.float32, device=self.device)
+        else:
+            direction = torch.as_tensor(check_direction).to(device=self.device, dtype=torch.float32)
+            if direction.numel() != 3:
+                raise ValueError(f"check_direction must hold three numbers, got shape {tuple(direction.shape)}")
+            direction = direction.reshape(3)
+        return flat, direction, b
+
+    def contains_points(self, points, check_direction=None) -> torch.Tensor:
+        """bool[*b]: is each of points [*b, 3] inside some instance -- one launch (tr_scene_points_any).  A point is inside
+        instance k when the rays (p, d) and (p, -d), taken into the instance's frame, each cross an odd number of the
+        member's triangles: RayMeshIntersector.contains_points per placed copy, without baking the copies (containment is
+        invariant under an invertible affine map).  d is check_direction, or the reference's default direction.  There is
+        no box test, no `broken` flag and no retry direction: an OPEN member contains nothing on the side where one of the
+        two rays escapes.  A point or a direction with a NaN or an infinity is inside nothing."""
+        flat, direction, b = self._points(points, check_direction)
+        return hops.scene_points_any_native(self._handle, self.device.index, flat, direction).reshape(b)
+
+    def contains_count(self, points, check_direction=None) -> torch.Tensor:
+        """int32[*b]: how many instances each point is inside (tr_scene_points_count); see contains_points.  Two instances
+        with the same placement count twice."""
+        flat, direction, b = self._points(points, check_direction)
+        return hops.scene_points_count_native(self._handle, self.device.index, flat, direction).reshape(b)
+
+    def containing_instances(self, points, check_direction=None):
+        """(offsets int64[n + 1], instance int32[h]) for the points flattened in order: the instances that hold point i are
+        instance[offsets[i]:offsets[i + 1]], ascending, uncapped; see contains_points.  One count launch, one scan, one host
+        read of the total to size the output, one fill."""
+        flat, direction, _ = self._points(points, check_direction)
+        return hops.scene_points_list_native(self._handle, self.device.index, flat, direction)
