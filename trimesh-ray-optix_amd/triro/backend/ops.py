@@ -1276,6 +1276,114 @@ def faces_meeting_triangles_native(accel_structure, tri, stack_entries=0):
     return offsets, face
 
 
+# --- the faces that each plane meets or cuts, and the section segments (include/triro_planes.h, csrc/planes.hip) -----------
+_PLANES_LIB_NAME = "libtriro_planes.so"
+PLANES_ABI_VERSION = 1    # TR_PLANES_ABI_VERSION of include/triro_planes.h
+_planes_module = None
+
+# every symbol include/triro_planes.h declares: (restype, argtypes)
+PLANES_ABI = {
+    "tr_planes_abi_version": (_int, []),
+    "tr_planes_frontier_capacity": (_int, []),
+    "tr_planes_any": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _vp]),
+    "tr_planes_count": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _vp]),
+    "tr_planes_fill": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _int, _int, _vp]),
+    "tr_planes_order": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp]),
+}
+
+
+def planes_library_path() -> str:
+    return os.environ.get("TRIRO_PLANES_LIBRARY") or os.path.join(os.path.dirname(library_path()), _PLANES_LIB_NAME)
+
+
+def get_planes_module():
+    """libtriro_planes.so.  Raises when it is not built or does not match this binding."""
+    global _planes_module
+    if _planes_module is None:
+        get_module()                       # libtriro_hip.so first: the planes library links against it
+        path = planes_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
+                               f"There is no torch fallback.")
+        lib = C.CDLL(path)
+        for name, (res, args) in PLANES_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.tr_planes_abi_version() != PLANES_ABI_VERSION:
+            raise RuntimeError(f"libtriro_planes.so ABI version {lib.tr_planes_abi_version()} != {PLANES_ABI_VERSION} expected by this binding")
+        _planes_module = lib
+    return _planes_module
+
+
+def _planes_args(accel_structure, origins, normals):
+    """(handle, contiguous origins, contiguous normals, n, device)"""
+    for name, t in (("origins", origins), ("normals", normals)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
+    if normals.device != origins.device or normals.shape != origins.shape:
+        raise ValueError(f"origins {tuple(origins.shape)} on {origins.device} and normals {tuple(normals.shape)} on {normals.device} "
+                         f"must have one shape and one device")
+    return _handle(accel_structure, origins), origins.contiguous(), normals.contiguous(), origins.shape[0], origins.device
+
+
+def planes_native(accel_structure, origins, normals, query="any", cut=False, frontier_entries=0) -> torch.Tensor:
+    """tr_planes_any (query="any": bool[n]) / tr_planes_count (query="count": int32[n]) for the planes (origin, normal), float32
+    [n, 3] each, on the handle's GPU.  cut: the faces the plane CUTS (those that own a row of the section) instead of the faces
+    it meets.  frontier_entries: 0 = the whole frontier, 1 .. capacity for tests (same results).  Nothing is allocated by the
+    library and nothing is synchronised."""
+    if query not in ("any", "count"):
+        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
+    lib = get_planes_module()
+    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
+    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    with torch.cuda.device(dev):
+        fn = lib.tr_planes_any if query == "any" else lib.tr_planes_count
+        _check(fn(handle, origins.data_ptr(), normals.data_ptr(), n, out.data_ptr(), 1 if cut else 0, int(frontier_entries),
+                  _stream_ptr(dev)))
+    return out
+
+
+def planes_fill_native(accel_structure, origins, normals, count, offsets, total, cut=False, want_segments=False, frontier_entries=0):
+    """tr_planes_fill: (face int32[total], segments float32[total, 2, 3] or None), the faces of plane i ascending at rows
+    offsets[i] .. offsets[i] + count[i].  count int32[n] is planes_native(..., "count", cut) and offsets int64[n] its exclusive
+    scan (tr_hits_scan) for the same planes; total (a Python int) sizes the outputs.  Segments need cut.  Nothing is allocated
+    by the library and nothing is synchronised."""
+    lib = get_planes_module()
+    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the planes' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    if want_segments and not cut:
+        raise ValueError("segments are those of the cut faces: want_segments needs cut=True")
+    face = _new_output((total,), torch.int32, dev)
+    segments = _new_output((total, 2, 3), torch.float32, dev) if want_segments else None
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib.tr_planes_fill(handle, origins.data_ptr(), normals.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
+                                  ptr(face), ptr(segments), 1 if cut else 0, int(frontier_entries), _stream_ptr(dev)))
+    return face, segments
+
+
+def faces_on_planes_native(accel_structure, origins, normals, cut=False, want_segments=False, frontier_entries=0):
+    """(offsets int64[n + 1], face, segments or None): one count launch, one scan, one host read of the total to size the
+    outputs (as faces_in_boxes_native), one fill."""
+    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
+    count = planes_native(accel_structure, origins, normals, "count", cut, frontier_entries)
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    face, segments = planes_fill_native(accel_structure, origins, normals, count, offsets[:n], int(total.value), cut, want_segments,
+                                        frontier_entries)
+    return offsets, face, segments
+
+
 # --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
 _CROSS_LIB_NAME = "libtriro_cross.so"
 CROSS_ABI_VERSION = 1    # TR_CROSS_ABI_VERSION of include/triro_cross.h

@@ -466,6 +466,77 @@ class RayMeshIntersector:
             found.append(ijk[met] + base)
         return torch.cat(found) if found else empty
 
+    # -- plane queries (libtriro_planes.so, include/triro_planes.h; not in the reference) -----
+    def _query_planes(self, origins, normals):
+        """origins, normals [*b, 3], broadcast against each other, as the native plane entries take them: (flat float32 origins
+        [n, 3], flat float32 normals [n, 3], the batch shape).  Conversion and device rules are those of _query_boxes."""
+        dev = self.mesh_vertices.device
+        parts = []
+        for name, x in (("origins", origins), ("normals", normals)):
+            if isinstance(x, torch.Tensor):
+                if not x.is_cuda:
+                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
+                if x.device != dev:
+                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
+                                     f"move it or build the intersector on that device")
+            t = _to_device_tensor(x, torch.float32, dev)
+            if t.dim() < 1 or t.shape[-1] != 3:
+                raise ValueError(f"{name} must have shape [*b, 3], got {tuple(t.shape)}")
+            parts.append(t)
+        try:
+            shape = torch.broadcast_shapes(parts[0].shape, parts[1].shape)
+        except RuntimeError:
+            raise ValueError(f"origins of shape {tuple(parts[0].shape)} and normals of shape {tuple(parts[1].shape)} do not broadcast") from None
+        origins, normals = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in parts)
+        return origins, normals, shape[:-1]
+
+    def planes_any(self, origins, normals) -> torch.Tensor:
+        """bool[*b]: does any triangle meet the plane through `origins` with the normal `normals` -- one launch of
+        libtriro_planes.so (tr_planes_any), one wave per plane.  origins and normals are [*b, 3] and broadcast against each
+        other; the normal need not be a unit vector.  A triangle MEETS a plane unless its vertices lie strictly on one side,
+        touching included (csrc/tr_planes.h has the predicate).  A plane with a NaN, an infinity or a zero normal meets nothing,
+        and a triangle with a non-finite coordinate is never met."""
+        origins, normals, b = self._query_planes(origins, normals)
+        return hops.planes_native(self.as_wrapper, origins, normals, "any").reshape(b)
+
+    def planes_count(self, origins, normals, cut=False) -> torch.Tensor:
+        """int32[*b]: how many triangles meet each plane (tr_planes_count), or with cut=True how many it CUTS: the triangles that
+        own a segment of the section; see planes_any and section_segments"""
+        origins, normals, b = self._query_planes(origins, normals)
+        return hops.planes_native(self.as_wrapper, origins, normals, "count", cut).reshape(b)
+
+    def faces_on_planes(self, origins, normals, cut=False):
+        """(offsets int64[n + 1], tri_idx int32[h]) for the planes flattened in order -- the triangles that meet (cut=True: are
+        cut by) plane i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped.  One count launch, one scan, one host read
+        of the total to size the outputs, one fill."""
+        origins, normals, b = self._query_planes(origins, normals)
+        offsets, face, _ = hops.faces_on_planes_native(self.as_wrapper, origins, normals, cut)
+        return offsets, face
+
+    def section_segments(self, origins, normals):
+        """(offsets int64[n + 1], tri_idx int32[h], segments float32[h, 2, 3]): the section of the mesh by each plane, as
+        trimesh.intersections.mesh_plane returns it -- one segment (p0, p1) per CUT triangle, ascending by triangle, directed
+        along (face normal) x (plane normal).  The section is the boundary of the surface strictly on the positive side of the
+        plane: a triangle lying in the plane owns nothing, an edge lying in it belongs to the triangle whose third vertex is on
+        the positive side.  A crossing point is interpolated from the negative to the positive end of its edge, so the two
+        triangles of an edge agree on it bit for bit and the segments of a closed mesh close into loops exactly.  Launches as
+        faces_on_planes."""
+        origins, normals, b = self._query_planes(origins, normals)
+        return hops.faces_on_planes_native(self.as_wrapper, origins, normals, True, True)
+
+    def section_multiplane(self, origin, normal, heights):
+        """section_segments for the planes at `heights` [m] along `normal` from `origin` (the shape of
+        trimesh.intersections.mesh_multiplane): plane k has the origin float32(origin + heights[k] * normal), evaluated in
+        float64, and the given normal.  Host code on section_segments."""
+        dev = self.mesh_vertices.device
+        o = _to_device_tensor(origin, torch.float64, dev)
+        nrm = _to_device_tensor(normal, torch.float64, dev)
+        h = _to_device_tensor(heights, torch.float64, dev)
+        if tuple(o.shape) != (3,) or tuple(nrm.shape) != (3,) or h.dim() != 1:
+            raise ValueError(f"origin and normal must have shape [3] and heights [m], got {tuple(o.shape)}, {tuple(nrm.shape)}, {tuple(h.shape)}")
+        origins = (o[None, :] + h[:, None] * nrm[None, :]).to(torch.float32)
+        return self.section_segments(origins, nrm.to(torch.float32))
+
     # -- triangle queries (libtriro_tris.so, include/triro_tris.h; not in the reference) ------
     def _query_triangles(self, triangles):
         """triangles [*b, 3, 3] as the native triangle entries take them: (flat float32 [n, 3, 3], the batch shape).  Conversion
