@@ -547,10 +547,102 @@ def set_option(name: str, value: int):
     _check(get_module().tr_set_option(name.encode(), int(value)))
 
 
-# --- the native N-rank step (include/triro_rccl.h, csrc/gather_rccl.cpp) --------------------------------------------
-_RCCL_LIB_NAME = "libtriro_rccl.so"
-_rccl_module = None
+# --- the satellite libraries libtriro_<key>.so: one loader, one list protocol, the shared argument checks -------------------
+class _Satellite:
+    """One library libtriro_<key>.so beside libtriro_hip.so: its ABI table {symbol: (restype, argtypes)} and the loader of
+    the library whose handles it works on.  The file name, the TRIRO_<KEY>_LIBRARY override, the version symbol
+    tr_<key>_abi_version and the expected <KEY>_ABI_VERSION of this module (read when the library is loaded; None: the
+    library has no version symbol) follow from the key.  Each section below registers its library in one line and binds
+    the public names x_library_path / get_x_module to it."""
 
+    def __init__(self, key, abi, prerequisite):
+        self.key, self.abi, self.prerequisite, self.lib = key, abi, prerequisite, None
+
+    def path(self) -> str:
+        return os.environ.get(f"TRIRO_{self.key.upper()}_LIBRARY") or \
+            os.path.join(os.path.dirname(library_path()), f"libtriro_{self.key}.so")
+
+    def load(self):
+        """The library, loaded once per process.  Raises when it is not built or does not match this binding."""
+        if self.lib is None:
+            self.prerequisite()                # libtriro_hip.so (and libtriro_scene.so) first: the library links against it
+            path = self.path()
+            if not os.path.exists(path):
+                raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build())")
+            lib = C.CDLL(path)
+            for name, (res, args) in self.abi.items():
+                fn = getattr(lib, name)   # AttributeError if the library lacks a declared symbol
+                fn.restype = res
+                fn.argtypes = args
+            want = globals()[f"{self.key.upper()}_ABI_VERSION"]
+            if want is not None:
+                have = getattr(lib, f"tr_{self.key}_abi_version")()
+                if have != want:
+                    raise RuntimeError(f"libtriro_{self.key}.so ABI version {have} != {want} expected by this binding")
+            self.lib = lib
+        return self.lib
+
+
+def _ptr(t):
+    """the device pointer of an optional tensor: None if absent"""
+    return t.data_ptr() if t is not None else None
+
+
+def _ptr_rows(t):
+    """the device pointer of an optional output of a fill: None if absent or empty (the fills take NULL for zero rows)"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _check_points(points):
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
+            points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+
+
+def _check_pair(name_a, a, name_b, b):
+    """two float32 GPU tensors [n, 3] of one shape on one device (the corners of boxes, the origins and normals of planes)"""
+    for name, t in ((name_a, a), (name_b, b)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
+    if b.device != a.device or b.shape != a.shape:
+        raise ValueError(f"{name_a} {tuple(a.shape)} on {a.device} and {name_b} {tuple(b.shape)} on {b.device} "
+                         f"must have one shape and one device")
+
+
+def _any_or_count(query, satellite):
+    """(the dtype of the output, the entry point) of the any / count pair of a library: bool and tr_<key>_any, or int32 and
+    tr_<key>_count"""
+    if query not in ("any", "count"):
+        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
+    return (torch.bool if query == "any" else torch.int32), getattr(satellite.load(), f"tr_{satellite.key}_{query}")
+
+
+def _scan_counts(count):
+    """(offsets int64[n + 1], total) of a flat int32[n] count: the exclusive scan that a fill takes as offsets[:n], and one
+    host read of the total to size its outputs (as intersects_location)."""
+    n, dev = count.shape[0], count.device
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    with torch.cuda.device(dev):
+        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
+        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
+                                         C.byref(total), _stream_ptr(dev)))
+    return offsets, int(total.value)
+
+
+def _check_fill(count, offsets, total, n, dev, whose) -> int:
+    """what every fill is given besides its queries: count int32[n], offsets int64[n] on the device of `whose` (the noun of
+    the queries), and the total, returned as an int"""
+    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the {whose}' device")
+    total = int(total)
+    if total < 0:
+        raise ValueError("total must not be negative")
+    return total
+
+
+# --- the native N-rank step (include/triro_rccl.h, csrc/gather_rccl.cpp) --------------------------------------------
 
 class TrShardStep(C.Structure):
     """tr_shard_step of include/triro_rccl.h"""
@@ -565,31 +657,24 @@ STEP_NO_EXCHANGE, STEP_LOOPBACK, STEP_TEST_DROP_SEND = 1, 2, 4
 COMM_ID_BYTES = 128
 
 
-def rccl_library_path() -> str:
-    return os.environ.get("TRIRO_RCCL_LIBRARY") or os.path.join(os.path.dirname(library_path()), _RCCL_LIB_NAME)
+RCCL_ABI_VERSION = None    # include/triro_rccl.h declares no version symbol
 
+# the symbols of include/triro_rccl.h this binding calls: (restype, argtypes)
+RCCL_ABI = {
+    "tr_rccl_last_error": (C.c_char_p, []),
+    "tr_rccl_available": (_int, []),
+    "tr_comm_unique_id": (_int, [_vp]),
+    "tr_comm_create": (_int, [_vp, _int, _int, _int, C.POINTER(_vp)]),
+    "tr_comm_destroy": (_int, [_vp]),
+    "tr_comm_abort": (_int, [_vp]),
+    "tr_sharded_closest_step": (_int, [_vp, _vp, C.POINTER(TrShardStep)]),
+}
 
-def get_rccl_module():
-    """libtriro_rccl.so (one C call per pipelined step of a ray-sharded closest-hit query).  Raises when it is not built;
-    whether RCCL itself can be found is a question for rccl_available()."""
-    global _rccl_module
-    if _rccl_module is None:
-        get_module()                       # libtriro_hip.so first: the step library links against it
-        path = rccl_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build())")
-        lib = C.CDLL(path)
-        lib.tr_rccl_last_error.restype = C.c_char_p
-        lib.tr_rccl_available.restype = _int
-        lib.tr_comm_unique_id.argtypes = [C.c_void_p]
-        lib.tr_comm_create.argtypes = [C.c_void_p, _int, _int, _int, C.POINTER(_vp)]
-        lib.tr_comm_destroy.argtypes = [_vp]
-        lib.tr_comm_abort.argtypes = [_vp]
-        lib.tr_sharded_closest_step.argtypes = [_vp, _vp, C.POINTER(TrShardStep)]
-        for f in ("tr_comm_unique_id", "tr_comm_create", "tr_comm_destroy", "tr_comm_abort", "tr_sharded_closest_step"):
-            getattr(lib, f).restype = _int
-        _rccl_module = lib
-    return _rccl_module
+# one C call per pipelined step of a ray-sharded closest-hit query.  get_rccl_module raises when the library is not built;
+# whether RCCL itself can be found is a question for rccl_available()
+_rccl = _Satellite("rccl", RCCL_ABI, get_module)
+rccl_library_path = _rccl.path
+get_rccl_module = _rccl.load
 
 
 def rccl_available() -> bool:
@@ -605,9 +690,7 @@ def _check_rccl(rc: int):
 
 
 # --- contains_points as one launch (include/triro_points.h, csrc/points.hip) ------------------------------------------
-_POINTS_LIB_NAME = "libtriro_points.so"
 POINTS_ABI_VERSION = 1    # TR_POINTS_ABI_VERSION of include/triro_points.h
-_points_module = None
 
 # every symbol include/triro_points.h declares: (restype, argtypes)
 POINTS_ABI = {
@@ -617,27 +700,9 @@ POINTS_ABI = {
 }
 
 
-def points_library_path() -> str:
-    return os.environ.get("TRIRO_POINTS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _POINTS_LIB_NAME)
-
-
-def get_points_module():
-    """libtriro_points.so.  Raises when it is not built or does not match this binding."""
-    global _points_module
-    if _points_module is None:
-        get_module()                       # libtriro_hip.so first: the points library links against it
-        path = points_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build())")
-        lib = C.CDLL(path)
-        for name, (res, args) in POINTS_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_points_abi_version() != POINTS_ABI_VERSION:
-            raise RuntimeError(f"libtriro_points.so ABI version {lib.tr_points_abi_version()} != {POINTS_ABI_VERSION} expected by this binding")
-        _points_module = lib
-    return _points_module
+_points = _Satellite("points", POINTS_ABI, get_module)
+points_library_path = _points.path
+get_points_module = _points.load
 
 
 def contains_addressing(accel_structure) -> int:
@@ -649,9 +714,7 @@ def contains_points_native(accel_structure, points, direction, box_lo, box_hi, w
     """tr_contains_points: (inside bool[n], broken bool[n], counts int32[2, n] or None, summary int64[2] = {points in the
     box, broken points}) for float32 points [n, 3] and 3-float device tensors direction / box_lo / box_hi (both boxes None:
     no box test).  Nothing is synchronised: the caller reads `summary` when it needs it."""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
-            points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    _check_points(points)
     dev = points.device
     handle = _handle(accel_structure, points)
     points = points.contiguous()
@@ -672,17 +735,13 @@ def contains_points_native(accel_structure, points, direction, box_lo, box_hi, w
     summary = _new_output((2,), torch.int64, dev)
     with torch.cuda.device(dev):
         _check(get_points_module().tr_contains_points(
-            handle, points.data_ptr(), n, direction.data_ptr(),
-            box_lo.data_ptr() if box_lo is not None else None, box_hi.data_ptr() if box_hi is not None else None,
-            inside.data_ptr(), broken.data_ptr(), counts.data_ptr() if counts is not None else None,
-            summary.data_ptr(), None, _stream_ptr(dev)))
+            handle, points.data_ptr(), n, direction.data_ptr(), _ptr(box_lo), _ptr(box_hi),
+            inside.data_ptr(), broken.data_ptr(), _ptr(counts), summary.data_ptr(), None, _stream_ptr(dev)))
     return inside, broken, counts, summary
 
 
 # --- closest_point as one launch (include/triro_nearest.h, csrc/nearest.hip) -------------------------------------------
-_NEAREST_LIB_NAME = "libtriro_nearest.so"
 NEAREST_ABI_VERSION = 1    # TR_NEAREST_ABI_VERSION of include/triro_nearest.h
-_nearest_module = None
 
 # every symbol include/triro_nearest.h declares: (restype, argtypes)
 NEAREST_ABI = {
@@ -692,37 +751,16 @@ NEAREST_ABI = {
 }
 
 
-def nearest_library_path() -> str:
-    return os.environ.get("TRIRO_NEAREST_LIBRARY") or os.path.join(os.path.dirname(library_path()), _NEAREST_LIB_NAME)
-
-
-def get_nearest_module():
-    """libtriro_nearest.so.  Raises when it is not built or does not match this binding."""
-    global _nearest_module
-    if _nearest_module is None:
-        get_module()                       # libtriro_hip.so first: the nearest library links against it
-        path = nearest_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in NEAREST_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_nearest_abi_version() != NEAREST_ABI_VERSION:
-            raise RuntimeError(f"libtriro_nearest.so ABI version {lib.tr_nearest_abi_version()} != {NEAREST_ABI_VERSION} expected by this binding")
-        _nearest_module = lib
-    return _nearest_module
+_nearest = _Satellite("nearest", NEAREST_ABI, get_module)
+nearest_library_path = _nearest.path
+get_nearest_module = _nearest.load
 
 
 def closest_point_native(accel_structure, points, stack_entries=0, want_closest=True, want_distance=True):
     """tr_closest_point: (closest float32[n, 3] or None, distance float32[n] or None, tri int32[n]) for float32 points
     [n, 3] on the handle's GPU.  stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).
     Nothing is allocated by the library and nothing is synchronised."""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
-            points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    _check_points(points)
     lib = get_nearest_module()
     dev = points.device
     handle = _handle(accel_structure, points)
@@ -732,16 +770,13 @@ def closest_point_native(accel_structure, points, stack_entries=0, want_closest=
     distance = _new_output((n,), torch.float32, dev) if want_distance else None
     tri = _new_output((n,), torch.int32, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_closest_point(handle, points.data_ptr(), n, closest.data_ptr() if closest is not None else None,
-                                    distance.data_ptr() if distance is not None else None, tri.data_ptr(),
+        _check(lib.tr_closest_point(handle, points.data_ptr(), n, _ptr(closest), _ptr(distance), tri.data_ptr(),
                                     int(stack_entries), _stream_ptr(dev)))
     return closest, distance, tri
 
 
 # --- any / closest on a per-ray interval [tmin, tmax] (include/triro_range.h, csrc/range.hip) --------------------------
-_RANGE_LIB_NAME = "libtriro_range.so"
 RANGE_ABI_VERSION = 1    # TR_RANGE_ABI_VERSION of include/triro_range.h
-_range_module = None
 
 # every symbol include/triro_range.h declares: (restype, argtypes)
 RANGE_ABI = {
@@ -752,28 +787,9 @@ RANGE_ABI = {
 }
 
 
-def range_library_path() -> str:
-    return os.environ.get("TRIRO_RANGE_LIBRARY") or os.path.join(os.path.dirname(library_path()), _RANGE_LIB_NAME)
-
-
-def get_range_module():
-    """libtriro_range.so.  Raises when it is not built or does not match this binding."""
-    global _range_module
-    if _range_module is None:
-        get_module()                       # libtriro_hip.so first: the range library links against it
-        path = range_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in RANGE_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_range_abi_version() != RANGE_ABI_VERSION:
-            raise RuntimeError(f"libtriro_range.so ABI version {lib.tr_range_abi_version()} != {RANGE_ABI_VERSION} expected by this binding")
-        _range_module = lib
-    return _range_module
+_range = _Satellite("range", RANGE_ABI, get_module)
+range_library_path = _range.path
+get_range_module = _range.load
 
 
 def _range_bound(t, name, n, dev):
@@ -798,8 +814,8 @@ def range_any_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
     out = _new_output(origins.shape[:-1], torch.bool, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_range_any(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
-                                tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_range_any(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
+                                _stream_ptr(dev)))
     return out
 
 
@@ -818,17 +834,14 @@ def range_closest_native(accel_structure, origins, dirs, tmin=None, tmax=None, s
     front = _new_output(b, torch.bool, dev) if want_dense else None
     loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
     uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
-    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_range_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), tri.data_ptr(), ptr(t), ptr(hit),
-                                    ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_range_closest(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), tri.data_ptr(), _ptr(t), _ptr(hit),
+                                    _ptr(front), _ptr(loc), _ptr(uv), int(stack_entries), _stream_ptr(dev)))
     return hit, front, tri, loc, uv, t
 
 
 # --- any / closest over placed copies of several meshes (include/triro_scene.h, csrc/scene.hip) --------------------------
-_SCENE_LIB_NAME = "libtriro_scene.so"
 SCENE_ABI_VERSION = 1    # TR_SCENE_ABI_VERSION of include/triro_scene.h
-_scene_module = None
 
 
 class TrSceneInfo(C.Structure):
@@ -849,28 +862,9 @@ SCENE_ABI = {
 }
 
 
-def scene_library_path() -> str:
-    return os.environ.get("TRIRO_SCENE_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_LIB_NAME)
-
-
-def get_scene_module():
-    """libtriro_scene.so.  Raises when it is not built or does not match this binding."""
-    global _scene_module
-    if _scene_module is None:
-        get_module()                       # libtriro_hip.so first: the scene library links against it
-        path = scene_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in SCENE_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_scene_abi_version() != SCENE_ABI_VERSION:
-            raise RuntimeError(f"libtriro_scene.so ABI version {lib.tr_scene_abi_version()} != {SCENE_ABI_VERSION} expected by this binding")
-        _scene_module = lib
-    return _scene_module
+_scene = _Satellite("scene", SCENE_ABI, get_module)
+scene_library_path = _scene.path
+get_scene_module = _scene.load
 
 
 def scene_create(device_index: int) -> int:
@@ -924,8 +918,8 @@ def scene_any_native(handle, device_index, origins, dirs, tmin=None, tmax=None, 
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
     out = _new_output(origins.shape[:-1], torch.bool, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_scene_any(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
-                                tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_scene_any(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
+                                _stream_ptr(dev)))
     return out
 
 
@@ -944,17 +938,14 @@ def scene_closest_native(handle, device_index, origins, dirs, tmin=None, tmax=No
     front = _new_output(b, torch.bool, dev) if want_dense else None
     loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
     uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
-    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_scene_closest(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), inst.data_ptr(), tri.data_ptr(), ptr(t),
-                                    ptr(hit), ptr(front), ptr(loc), ptr(uv), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_scene_closest(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), inst.data_ptr(), tri.data_ptr(), _ptr(t),
+                                    _ptr(hit), _ptr(front), _ptr(loc), _ptr(uv), int(stack_entries), _stream_ptr(dev)))
     return hit, front, inst, tri, t, loc, uv
 
 
 # --- the faces within a distance of each point (include/triro_within.h, csrc/within.hip) -------------------------------
-_WITHIN_LIB_NAME = "libtriro_within.so"
 WITHIN_ABI_VERSION = 1    # TR_WITHIN_ABI_VERSION of include/triro_within.h
-_within_module = None
 _f32 = C.c_float
 
 # every symbol include/triro_within.h declares: (restype, argtypes)
@@ -968,35 +959,14 @@ WITHIN_ABI = {
 }
 
 
-def within_library_path() -> str:
-    return os.environ.get("TRIRO_WITHIN_LIBRARY") or os.path.join(os.path.dirname(library_path()), _WITHIN_LIB_NAME)
-
-
-def get_within_module():
-    """libtriro_within.so.  Raises when it is not built or does not match this binding."""
-    global _within_module
-    if _within_module is None:
-        get_module()                       # libtriro_hip.so first: the within library links against it
-        path = within_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in WITHIN_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_within_abi_version() != WITHIN_ABI_VERSION:
-            raise RuntimeError(f"libtriro_within.so ABI version {lib.tr_within_abi_version()} != {WITHIN_ABI_VERSION} expected by this binding")
-        _within_module = lib
-    return _within_module
+_within = _Satellite("within", WITHIN_ABI, get_module)
+within_library_path = _within.path
+get_within_module = _within.load
 
 
 def _within_args(accel_structure, points, radius):
     """(handle, contiguous points, n, device, radius pointer or None, scalar radius, the radius tensor kept alive)"""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
-            points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    _check_points(points)
     dev, n = points.device, points.shape[0]
     handle = _handle(accel_structure, points)
     if isinstance(radius, torch.Tensor):
@@ -1012,13 +982,10 @@ def within_native(accel_structure, points, radius, query="any", stack_entries=0)
     """tr_within_any (query="any": bool[n]) / tr_within_count (query="count": int32[n]) for float32 points [n, 3] on the
     handle's GPU.  radius: a number, or a dense float32 [n] tensor on that GPU.  stack_entries: 0 = the whole stack,
     1 .. capacity for tests (same results).  Nothing is allocated by the library and nothing is synchronised."""
-    if query not in ("any", "count"):
-        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
-    lib = get_within_module()
+    dtype, fn = _any_or_count(query, _within)
     handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
-    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    out = _new_output((n,), dtype, dev)
     with torch.cuda.device(dev):
-        fn = lib.tr_within_any if query == "any" else lib.tr_within_count
         _check(fn(handle, points.data_ptr(), n, rptr, r, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
     return out
 
@@ -1031,20 +998,14 @@ def within_fill_native(accel_structure, points, radius, count, offsets, total, w
     outputs.  Nothing is allocated by the library and nothing is synchronised."""
     lib = get_within_module()
     handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the points' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "points")
     face = _new_output((total,), torch.int32, dev)
     distance = _new_output((total,), torch.float32, dev) if want_distance else None
     closest = _new_output((total, 3), torch.float32, dev) if want_closest else None
     slot = _new_output((total,), torch.int32, dev) if (want_distance or want_closest) and total > 0 else None
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_within_fill(handle, points.data_ptr(), n, rptr, r, count.data_ptr(), offsets.data_ptr(), total, ptr(face),
-                                  ptr(distance), ptr(closest), ptr(slot), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_within_fill(handle, points.data_ptr(), n, rptr, r, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
+                                  _ptr_rows(distance), _ptr_rows(closest), _ptr_rows(slot), int(stack_entries), _stream_ptr(dev)))
     return face, distance, closest
 
 
@@ -1054,13 +1015,8 @@ def faces_within_native(accel_structure, points, radius, want_distance=False, wa
     handle, points, n, dev, rptr, r, keep = _within_args(accel_structure, points, radius)
     radius = keep if keep is not None else r
     count = within_native(accel_structure, points, radius, "count", stack_entries)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    face, distance, closest = within_fill_native(accel_structure, points, radius, count, offsets[:n], int(total.value),
+    offsets, total = _scan_counts(count)
+    face, distance, closest = within_fill_native(accel_structure, points, radius, count, offsets[:n], total,
                                                  want_distance, want_closest, stack_entries)
     return offsets, face, distance, closest
 
@@ -1074,16 +1030,13 @@ def within_closest_native(accel_structure, points, radius, stack_entries=0, want
     distance = _new_output((n,), torch.float32, dev) if want_distance else None
     tri = _new_output((n,), torch.int32, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_within_closest(handle, points.data_ptr(), n, rptr, r, closest.data_ptr() if closest is not None else None,
-                                     distance.data_ptr() if distance is not None else None, tri.data_ptr(),
+        _check(lib.tr_within_closest(handle, points.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), tri.data_ptr(),
                                      int(stack_entries), _stream_ptr(dev)))
     return closest, distance, tri
 
 
 # --- the faces that meet each axis-aligned box (include/triro_boxes.h, csrc/boxes.hip) ------------------------------------
-_BOXES_LIB_NAME = "libtriro_boxes.so"
 BOXES_ABI_VERSION = 1    # TR_BOXES_ABI_VERSION of include/triro_boxes.h
-_boxes_module = None
 
 # every symbol include/triro_boxes.h declares: (restype, argtypes)
 BOXES_ABI = {
@@ -1095,37 +1048,14 @@ BOXES_ABI = {
 }
 
 
-def boxes_library_path() -> str:
-    return os.environ.get("TRIRO_BOXES_LIBRARY") or os.path.join(os.path.dirname(library_path()), _BOXES_LIB_NAME)
-
-
-def get_boxes_module():
-    """libtriro_boxes.so.  Raises when it is not built or does not match this binding."""
-    global _boxes_module
-    if _boxes_module is None:
-        get_module()                       # libtriro_hip.so first: the boxes library links against it
-        path = boxes_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in BOXES_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_boxes_abi_version() != BOXES_ABI_VERSION:
-            raise RuntimeError(f"libtriro_boxes.so ABI version {lib.tr_boxes_abi_version()} != {BOXES_ABI_VERSION} expected by this binding")
-        _boxes_module = lib
-    return _boxes_module
+_boxes = _Satellite("boxes", BOXES_ABI, get_module)
+boxes_library_path = _boxes.path
+get_boxes_module = _boxes.load
 
 
 def _boxes_args(accel_structure, lo, hi):
     """(handle, contiguous lo, contiguous hi, n, device)"""
-    for name, t in (("lo", lo), ("hi", hi)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
-    if hi.device != lo.device or hi.shape != lo.shape:
-        raise ValueError(f"lo {tuple(lo.shape)} on {lo.device} and hi {tuple(hi.shape)} on {hi.device} must have one shape and one device")
+    _check_pair("lo", lo, "hi", hi)
     return _handle(accel_structure, lo), lo.contiguous(), hi.contiguous(), lo.shape[0], lo.device
 
 
@@ -1133,13 +1063,10 @@ def boxes_native(accel_structure, lo, hi, query="any", stack_entries=0) -> torch
     """tr_boxes_any (query="any": bool[n]) / tr_boxes_count (query="count": int32[n]) for the closed boxes [lo, hi], float32
     [n, 3] each, on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing
     is allocated by the library and nothing is synchronised."""
-    if query not in ("any", "count"):
-        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
-    lib = get_boxes_module()
+    dtype, fn = _any_or_count(query, _boxes)
     handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
-    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    out = _new_output((n,), dtype, dev)
     with torch.cuda.device(dev):
-        fn = lib.tr_boxes_any if query == "any" else lib.tr_boxes_count
         _check(fn(handle, lo.data_ptr(), hi.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
     return out
 
@@ -1151,18 +1078,12 @@ def boxes_fill_native(accel_structure, lo, hi, count, offsets, total, want_insid
     nothing is synchronised."""
     lib = get_boxes_module()
     handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the boxes' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "boxes")
     face = _new_output((total,), torch.int32, dev)
     inside = _new_output((total,), torch.bool, dev) if want_inside else None
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_boxes_fill(handle, lo.data_ptr(), hi.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, ptr(face),
-                                 ptr(inside), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_boxes_fill(handle, lo.data_ptr(), hi.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
+                                 _ptr_rows(inside), int(stack_entries), _stream_ptr(dev)))
     return face, inside
 
 
@@ -1171,20 +1092,13 @@ def faces_in_boxes_native(accel_structure, lo, hi, want_inside=False, stack_entr
     outputs (as faces_within_native), one fill."""
     handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
     count = boxes_native(accel_structure, lo, hi, "count", stack_entries)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    face, inside = boxes_fill_native(accel_structure, lo, hi, count, offsets[:n], int(total.value), want_inside, stack_entries)
+    offsets, total = _scan_counts(count)
+    face, inside = boxes_fill_native(accel_structure, lo, hi, count, offsets[:n], total, want_inside, stack_entries)
     return offsets, face, inside
 
 
 # --- the faces that meet each query triangle (include/triro_tris.h, csrc/tris.hip) ----------------------------------------
-_TRIS_LIB_NAME = "libtriro_tris.so"
 TRIS_ABI_VERSION = 1    # TR_TRIS_ABI_VERSION of include/triro_tris.h
-_tris_module = None
 
 # every symbol include/triro_tris.h declares: (restype, argtypes)
 TRIS_ABI = {
@@ -1196,28 +1110,9 @@ TRIS_ABI = {
 }
 
 
-def tris_library_path() -> str:
-    return os.environ.get("TRIRO_TRIS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _TRIS_LIB_NAME)
-
-
-def get_tris_module():
-    """libtriro_tris.so.  Raises when it is not built or does not match this binding."""
-    global _tris_module
-    if _tris_module is None:
-        get_module()                       # libtriro_hip.so first: the triangle library links against it
-        path = tris_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in TRIS_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_tris_abi_version() != TRIS_ABI_VERSION:
-            raise RuntimeError(f"libtriro_tris.so ABI version {lib.tr_tris_abi_version()} != {TRIS_ABI_VERSION} expected by this binding")
-        _tris_module = lib
-    return _tris_module
+_tris = _Satellite("tris", TRIS_ABI, get_module)
+tris_library_path = _tris.path
+get_tris_module = _tris.load
 
 
 def _tris_args(accel_structure, tri):
@@ -1231,13 +1126,10 @@ def tris_native(accel_structure, tri, query="any", stack_entries=0) -> torch.Ten
     """tr_tris_any (query="any": bool[n]) / tr_tris_count (query="count": int32[n]) for the query triangles, float32 [n, 3, 3],
     on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated
     by the library and nothing is synchronised."""
-    if query not in ("any", "count"):
-        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
-    lib = get_tris_module()
+    dtype, fn = _any_or_count(query, _tris)
     handle, tri, n, dev = _tris_args(accel_structure, tri)
-    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    out = _new_output((n,), dtype, dev)
     with torch.cuda.device(dev):
-        fn = lib.tr_tris_any if query == "any" else lib.tr_tris_count
         _check(fn(handle, tri.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
     return out
 
@@ -1248,16 +1140,11 @@ def tris_fill_native(accel_structure, tri, count, offsets, total, stack_entries=
     Python int) sizes the output.  Nothing is allocated by the library and nothing is synchronised."""
     lib = get_tris_module()
     handle, tri, n, dev = _tris_args(accel_structure, tri)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the triangles' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "triangles")
     face = _new_output((total,), torch.int32, dev)
     with torch.cuda.device(dev):
         _check(lib.tr_tris_fill(handle, tri.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
-                                face.data_ptr() if total else None, int(stack_entries), _stream_ptr(dev)))
+                                _ptr_rows(face), int(stack_entries), _stream_ptr(dev)))
     return face
 
 
@@ -1266,20 +1153,13 @@ def faces_meeting_triangles_native(accel_structure, tri, stack_entries=0):
     faces_in_boxes_native), one fill."""
     handle, tri, n, dev = _tris_args(accel_structure, tri)
     count = tris_native(accel_structure, tri, "count", stack_entries)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    face = tris_fill_native(accel_structure, tri, count, offsets[:n], int(total.value), stack_entries)
+    offsets, total = _scan_counts(count)
+    face = tris_fill_native(accel_structure, tri, count, offsets[:n], total, stack_entries)
     return offsets, face
 
 
 # --- the faces that each plane meets or cuts, and the section segments (include/triro_planes.h, csrc/planes.hip) -----------
-_PLANES_LIB_NAME = "libtriro_planes.so"
 PLANES_ABI_VERSION = 1    # TR_PLANES_ABI_VERSION of include/triro_planes.h
-_planes_module = None
 
 # every symbol include/triro_planes.h declares: (restype, argtypes)
 PLANES_ABI = {
@@ -1292,38 +1172,14 @@ PLANES_ABI = {
 }
 
 
-def planes_library_path() -> str:
-    return os.environ.get("TRIRO_PLANES_LIBRARY") or os.path.join(os.path.dirname(library_path()), _PLANES_LIB_NAME)
-
-
-def get_planes_module():
-    """libtriro_planes.so.  Raises when it is not built or does not match this binding."""
-    global _planes_module
-    if _planes_module is None:
-        get_module()                       # libtriro_hip.so first: the planes library links against it
-        path = planes_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in PLANES_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_planes_abi_version() != PLANES_ABI_VERSION:
-            raise RuntimeError(f"libtriro_planes.so ABI version {lib.tr_planes_abi_version()} != {PLANES_ABI_VERSION} expected by this binding")
-        _planes_module = lib
-    return _planes_module
+_planes = _Satellite("planes", PLANES_ABI, get_module)
+planes_library_path = _planes.path
+get_planes_module = _planes.load
 
 
 def _planes_args(accel_structure, origins, normals):
     """(handle, contiguous origins, contiguous normals, n, device)"""
-    for name, t in (("origins", origins), ("normals", normals)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
-    if normals.device != origins.device or normals.shape != origins.shape:
-        raise ValueError(f"origins {tuple(origins.shape)} on {origins.device} and normals {tuple(normals.shape)} on {normals.device} "
-                         f"must have one shape and one device")
+    _check_pair("origins", origins, "normals", normals)
     return _handle(accel_structure, origins), origins.contiguous(), normals.contiguous(), origins.shape[0], origins.device
 
 
@@ -1332,13 +1188,10 @@ def planes_native(accel_structure, origins, normals, query="any", cut=False, fro
     [n, 3] each, on the handle's GPU.  cut: the faces the plane CUTS (those that own a row of the section) instead of the faces
     it meets.  frontier_entries: 0 = the whole frontier, 1 .. capacity for tests (same results).  Nothing is allocated by the
     library and nothing is synchronised."""
-    if query not in ("any", "count"):
-        raise ValueError(f"query must be 'any' or 'count', got {query!r}")
-    lib = get_planes_module()
+    dtype, fn = _any_or_count(query, _planes)
     handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
-    out = _new_output((n,), torch.bool if query == "any" else torch.int32, dev)
+    out = _new_output((n,), dtype, dev)
     with torch.cuda.device(dev):
-        fn = lib.tr_planes_any if query == "any" else lib.tr_planes_count
         _check(fn(handle, origins.data_ptr(), normals.data_ptr(), n, out.data_ptr(), 1 if cut else 0, int(frontier_entries),
                   _stream_ptr(dev)))
     return out
@@ -1351,20 +1204,14 @@ def planes_fill_native(accel_structure, origins, normals, count, offsets, total,
     by the library and nothing is synchronised."""
     lib = get_planes_module()
     handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the planes' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "planes")
     if want_segments and not cut:
         raise ValueError("segments are those of the cut faces: want_segments needs cut=True")
     face = _new_output((total,), torch.int32, dev)
     segments = _new_output((total, 2, 3), torch.float32, dev) if want_segments else None
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
         _check(lib.tr_planes_fill(handle, origins.data_ptr(), normals.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
-                                  ptr(face), ptr(segments), 1 if cut else 0, int(frontier_entries), _stream_ptr(dev)))
+                                  _ptr_rows(face), _ptr_rows(segments), 1 if cut else 0, int(frontier_entries), _stream_ptr(dev)))
     return face, segments
 
 
@@ -1373,21 +1220,14 @@ def faces_on_planes_native(accel_structure, origins, normals, cut=False, want_se
     outputs (as faces_in_boxes_native), one fill."""
     handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
     count = planes_native(accel_structure, origins, normals, "count", cut, frontier_entries)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    face, segments = planes_fill_native(accel_structure, origins, normals, count, offsets[:n], int(total.value), cut, want_segments,
+    offsets, total = _scan_counts(count)
+    face, segments = planes_fill_native(accel_structure, origins, normals, count, offsets[:n], total, cut, want_segments,
                                         frontier_entries)
     return offsets, face, segments
 
 
 # --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
-_CROSS_LIB_NAME = "libtriro_cross.so"
 CROSS_ABI_VERSION = 1    # TR_CROSS_ABI_VERSION of include/triro_cross.h
-_cross_module = None
 
 # every symbol include/triro_cross.h declares: (restype, argtypes)
 CROSS_ABI = {
@@ -1398,28 +1238,9 @@ CROSS_ABI = {
 }
 
 
-def cross_library_path() -> str:
-    return os.environ.get("TRIRO_CROSS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _CROSS_LIB_NAME)
-
-
-def get_cross_module():
-    """libtriro_cross.so.  Raises when it is not built or does not match this binding."""
-    global _cross_module
-    if _cross_module is None:
-        get_module()                       # libtriro_hip.so first: the cross library links against it
-        path = cross_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in CROSS_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_cross_abi_version() != CROSS_ABI_VERSION:
-            raise RuntimeError(f"libtriro_cross.so ABI version {lib.tr_cross_abi_version()} != {CROSS_ABI_VERSION} expected by this binding")
-        _cross_module = lib
-    return _cross_module
+_cross = _Satellite("cross", CROSS_ABI, get_module)
+cross_library_path = _cross.path
+get_cross_module = _cross.load
 
 
 def cross_count_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
@@ -1434,8 +1255,8 @@ def cross_count_native(accel_structure, origins, dirs, tmin=None, tmax=None, sta
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
     out = _new_output(origins.shape[:-1], torch.int32, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_cross_count(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
-                                  tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_cross_count(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
+                                  _stream_ptr(dev)))
     return out
 
 
@@ -1451,12 +1272,7 @@ def cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets
     dev, n = origins.device, origins.numel() // 3
     handle = _handle(accel_structure, origins)
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the rays' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "rays")
     face = _new_output((total,), torch.int32, dev)
     t = _new_output((total,), torch.float32, dev)
     front = _new_output((total,), torch.bool, dev) if want_front else None
@@ -1464,11 +1280,10 @@ def cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets
     uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
     ray = _new_output((total,), torch.int64, dev) if want_ray else None
     slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_cross_fill(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), count.data_ptr(), offsets.data_ptr(), total,
-                                 ptr(face), ptr(t), ptr(front), ptr(loc), ptr(uv), ptr(ray), int(ray_base), ptr(slot), int(stack_entries),
-                                 _stream_ptr(dev)))
+        _check(lib.tr_cross_fill(handle, C.byref(make_rays(origins, dirs)), _ptr_rows(tmin), _ptr_rows(tmax), count.data_ptr(),
+                                 offsets.data_ptr(), total, _ptr_rows(face), _ptr_rows(t), _ptr_rows(front), _ptr_rows(loc),
+                                 _ptr_rows(uv), _ptr_rows(ray), int(ray_base), _ptr_rows(slot), int(stack_entries), _stream_ptr(dev)))
     return face, t, front, loc, uv, ray
 
 
@@ -1476,22 +1291,14 @@ def cross_all_native(accel_structure, origins, dirs, tmin=None, tmax=None, want_
                      want_ray=False, ray_base: int = 0, stack_entries=0):
     """(offsets int64[n + 1], face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened in order:
     one count launch, one scan, one host read of the total to size the outputs (as faces_within_native), one fill."""
-    n, dev = origins.numel() // 3, origins.device
     count = cross_count_native(accel_structure, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    return (offsets,) + cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value), want_front,
+    offsets, total = _scan_counts(count)
+    return (offsets,) + cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets[:-1], total, want_front,
                                           want_loc, want_uv, want_ray, ray_base, stack_entries)
 
 
 # --- every crossing of a world ray over an instanced scene (include/triro_scene_cross.h, csrc/scene_cross.hip) ------------
-_SCENE_CROSS_LIB_NAME = "libtriro_scene_cross.so"
 SCENE_CROSS_ABI_VERSION = 1    # TR_SCENE_CROSS_ABI_VERSION of include/triro_scene_cross.h
-_scene_cross_module = None
 
 # every symbol include/triro_scene_cross.h declares: (restype, argtypes)
 SCENE_CROSS_ABI = {
@@ -1502,29 +1309,9 @@ SCENE_CROSS_ABI = {
 }
 
 
-def scene_cross_library_path() -> str:
-    return os.environ.get("TRIRO_SCENE_CROSS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_CROSS_LIB_NAME)
-
-
-def get_scene_cross_module():
-    """libtriro_scene_cross.so.  Raises when it is not built or does not match this binding."""
-    global _scene_cross_module
-    if _scene_cross_module is None:
-        get_scene_module()                 # libtriro_hip.so and libtriro_scene.so first: the handles are theirs
-        path = scene_cross_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in SCENE_CROSS_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_scene_cross_abi_version() != SCENE_CROSS_ABI_VERSION:
-            raise RuntimeError(f"libtriro_scene_cross.so ABI version {lib.tr_scene_cross_abi_version()} != {SCENE_CROSS_ABI_VERSION} "
-                               f"expected by this binding")
-        _scene_cross_module = lib
-    return _scene_cross_module
+_scene_cross = _Satellite("scene_cross", SCENE_CROSS_ABI, get_scene_module)      # the scene handles are libtriro_scene.so's
+scene_cross_library_path = _scene_cross.path
+get_scene_cross_module = _scene_cross.load
 
 
 def scene_cross_count_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
@@ -1536,8 +1323,8 @@ def scene_cross_count_native(handle, device_index, origins, dirs, tmin=None, tma
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
     out = _new_output(origins.shape[:-1], torch.int32, dev)
     with torch.cuda.device(dev):
-        _check(lib.tr_scene_cross_count(handle, C.byref(make_rays(origins, dirs)), tmin.data_ptr() if tmin is not None else None,
-                                        tmax.data_ptr() if tmax is not None else None, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_scene_cross_count(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
+                                        _stream_ptr(dev)))
     return out
 
 
@@ -1552,12 +1339,7 @@ def scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, cou
     lib = get_scene_cross_module()
     dev, n = origins.device, origins.numel() // 3
     tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the rays' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "rays")
     inst = _new_output((total,), torch.int32, dev)
     face = _new_output((total,), torch.int32, dev)
     t = _new_output((total,), torch.float32, dev)
@@ -1566,11 +1348,11 @@ def scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, cou
     uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
     ray = _new_output((total,), torch.int64, dev) if want_ray else None
     slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
-        _check(lib.tr_scene_cross_fill(handle, C.byref(make_rays(origins, dirs)), ptr(tmin), ptr(tmax), count.data_ptr(), offsets.data_ptr(),
-                                       total, ptr(inst), ptr(face), ptr(t), ptr(front), ptr(loc), ptr(uv), ptr(ray), int(ray_base), ptr(slot),
-                                       int(stack_entries), _stream_ptr(dev)))
+        _check(lib.tr_scene_cross_fill(handle, C.byref(make_rays(origins, dirs)), _ptr_rows(tmin), _ptr_rows(tmax), count.data_ptr(),
+                                       offsets.data_ptr(), total, _ptr_rows(inst), _ptr_rows(face), _ptr_rows(t), _ptr_rows(front),
+                                       _ptr_rows(loc), _ptr_rows(uv), _ptr_rows(ray), int(ray_base), _ptr_rows(slot), int(stack_entries),
+                                       _stream_ptr(dev)))
     return inst, face, t, front, loc, uv, ray
 
 
@@ -1578,22 +1360,14 @@ def scene_cross_all_native(handle, device_index, origins, dirs, tmin=None, tmax=
                            want_ray=False, ray_base: int = 0, stack_entries=0):
     """(offsets int64[n + 1], instance, face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened
     in order: one count launch, one scan, one host read of the total to size the outputs, one fill: as cross_all_native."""
-    n, dev = origins.numel() // 3, origins.device
     count = scene_cross_count_native(handle, device_index, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    return (offsets,) + scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets[:n], int(total.value),
+    offsets, total = _scan_counts(count)
+    return (offsets,) + scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets[:-1], total,
                                                 want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)
 
 
 # --- which instances of a scene hold a point (include/triro_scene_points.h, csrc/scene_points.hip) -------------------------
-_SCENE_POINTS_LIB_NAME = "libtriro_scene_points.so"
 SCENE_POINTS_ABI_VERSION = 1    # TR_SCENE_POINTS_ABI_VERSION of include/triro_scene_points.h
-_scene_points_module = None
 
 # every symbol include/triro_scene_points.h declares: (restype, argtypes)
 SCENE_POINTS_ABI = {
@@ -1605,35 +1379,14 @@ SCENE_POINTS_ABI = {
 }
 
 
-def scene_points_library_path() -> str:
-    return os.environ.get("TRIRO_SCENE_POINTS_LIBRARY") or os.path.join(os.path.dirname(library_path()), _SCENE_POINTS_LIB_NAME)
-
-
-def get_scene_points_module():
-    """libtriro_scene_points.so.  Raises when it is not built or does not match this binding."""
-    global _scene_points_module
-    if _scene_points_module is None:
-        get_scene_module()                 # libtriro_hip.so and libtriro_scene.so first: the handles are theirs
-        path = scene_points_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build()). "
-                               f"There is no torch fallback.")
-        lib = C.CDLL(path)
-        for name, (res, args) in SCENE_POINTS_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.tr_scene_points_abi_version() != SCENE_POINTS_ABI_VERSION:
-            raise RuntimeError(f"libtriro_scene_points.so ABI version {lib.tr_scene_points_abi_version()} != {SCENE_POINTS_ABI_VERSION} "
-                               f"expected by this binding")
-        _scene_points_module = lib
-    return _scene_points_module
+_scene_points = _Satellite("scene_points", SCENE_POINTS_ABI, get_scene_module)   # the scene handles are libtriro_scene.so's
+scene_points_library_path = _scene_points.path
+get_scene_points_module = _scene_points.load
 
 
 def _scene_points_args(points, direction, device_index):
     """(contiguous points, contiguous direction, n, device)"""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    _check_points(points)
     if points.device.index != device_index:
         raise ValueError(f"points are on {points.device} but the scene lives on cuda:{device_index}; move the points")
     if not isinstance(direction, torch.Tensor) or direction.device != points.device or direction.dtype != torch.float32 or direction.numel() != 3:
@@ -1670,16 +1423,11 @@ def scene_points_fill_native(handle, device_index, points, direction, count, off
     library and nothing is synchronised."""
     lib = get_scene_points_module()
     points, direction, n, dev = _scene_points_args(points, direction, device_index)
-    for name, t, dt in (("count", count, torch.int32), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the points' device")
-    total = int(total)
-    if total < 0:
-        raise ValueError("total must not be negative")
+    total = _check_fill(count, offsets, total, n, dev, "points")
     inst = _new_output((total,), torch.int32, dev)
     with torch.cuda.device(dev):
         _check(lib.tr_scene_points_fill(handle, points.data_ptr(), n, direction.data_ptr(), count.data_ptr(), offsets.data_ptr(), total,
-                                        inst.data_ptr() if total else None, int(stack_entries), _stream_ptr(dev)))
+                                        _ptr_rows(inst), int(stack_entries), _stream_ptr(dev)))
     return inst
 
 
@@ -1688,10 +1436,5 @@ def scene_points_list_native(handle, device_index, points, direction, stack_entr
     (as faces_in_boxes_native), one fill."""
     points, direction, n, dev = _scene_points_args(points, direction, device_index)
     count = scene_points_count_native(handle, device_index, points, direction, stack_entries)
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    return offsets, scene_points_fill_native(handle, device_index, points, direction, count, offsets[:n], int(total.value), stack_entries)
+    offsets, total = _scan_counts(count)
+    return offsets, scene_points_fill_native(handle, device_index, points, direction, count, offsets[:n], total, stack_entries)

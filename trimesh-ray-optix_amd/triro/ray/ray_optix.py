@@ -358,12 +358,13 @@ class RayMeshIntersector:
         return (offsets, face) + ((distance,) if return_distance else ()) + ((closest,) if return_closest else ())
 
     # -- box queries (libtriro_boxes.so, include/triro_boxes.h; not in the reference) ---------
-    def _query_boxes(self, lo, hi):
-        """lo, hi [*b, 3], broadcast against each other, as the native box entries take them: (flat float32 lo [n, 3], flat
-        float32 hi [n, 3], the batch shape).  Conversion and device rules are those of _proximity_points, for each of the two."""
+    def _query_pair(self, first, second, names):
+        """Two arguments [*b, 3] called `names` (lo and hi of boxes, origins and normals of planes), broadcast against each
+        other, as the native box and plane entries take them: (flat float32 first [n, 3], flat float32 second [n, 3], the batch
+        shape).  Conversion and device rules are those of _proximity_points, for each of the two."""
         dev = self.mesh_vertices.device
-        corners = []
-        for name, x in (("lo", lo), ("hi", hi)):
+        parts = []
+        for name, x in zip(names, (first, second)):
             if isinstance(x, torch.Tensor):
                 if not x.is_cuda:
                     raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
@@ -373,32 +374,33 @@ class RayMeshIntersector:
             t = _to_device_tensor(x, torch.float32, dev)
             if t.dim() < 1 or t.shape[-1] != 3:
                 raise ValueError(f"{name} must have shape [*b, 3], got {tuple(t.shape)}")
-            corners.append(t)
+            parts.append(t)
         try:
-            shape = torch.broadcast_shapes(corners[0].shape, corners[1].shape)
+            shape = torch.broadcast_shapes(parts[0].shape, parts[1].shape)
         except RuntimeError:
-            raise ValueError(f"lo of shape {tuple(corners[0].shape)} and hi of shape {tuple(corners[1].shape)} do not broadcast") from None
-        lo, hi = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in corners)
-        return lo, hi, shape[:-1]
+            raise ValueError(f"{names[0]} of shape {tuple(parts[0].shape)} and {names[1]} of shape {tuple(parts[1].shape)} "
+                             f"do not broadcast") from None
+        first, second = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in parts)
+        return first, second, shape[:-1]
 
     def boxes_any(self, lo, hi) -> torch.Tensor:
         """bool[*b]: does any triangle meet the closed axis-aligned box [lo, hi] -- one launch of libtriro_boxes.so
         (tr_boxes_any).  lo and hi are [*b, 3] and broadcast against each other.  A triangle MEETS a box when they share a
         point, touching included (csrc/tr_boxes.h has the predicate).  Flat boxes, lines and points are boxes; a box with a NaN,
         an infinity or lo > hi on some axis meets nothing, and a triangle with a non-finite coordinate is never met."""
-        lo, hi, b = self._query_boxes(lo, hi)
+        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
         return hops.boxes_native(self.as_wrapper, lo, hi, "any").reshape(b)
 
     def boxes_count(self, lo, hi) -> torch.Tensor:
         """int32[*b]: how many triangles meet each box (tr_boxes_count); see boxes_any"""
-        lo, hi, b = self._query_boxes(lo, hi)
+        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
         return hops.boxes_native(self.as_wrapper, lo, hi, "count").reshape(b)
 
     def faces_in_boxes(self, lo, hi, return_inside=False):
         """(offsets int64[n + 1], tri_idx int32[h][, inside bool[h]]) for the boxes flattened in order -- the triangles that
         meet box i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped; inside[k] says that all three vertices of
         that triangle lie in the box.  One count launch, one scan, one host read of the total to size the outputs, one fill."""
-        lo, hi, b = self._query_boxes(lo, hi)
+        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
         offsets, face, inside = hops.faces_in_boxes_native(self.as_wrapper, lo, hi, return_inside)
         return (offsets, face) + ((inside,) if return_inside else ())
 
@@ -467,49 +469,26 @@ class RayMeshIntersector:
         return torch.cat(found) if found else empty
 
     # -- plane queries (libtriro_planes.so, include/triro_planes.h; not in the reference) -----
-    def _query_planes(self, origins, normals):
-        """origins, normals [*b, 3], broadcast against each other, as the native plane entries take them: (flat float32 origins
-        [n, 3], flat float32 normals [n, 3], the batch shape).  Conversion and device rules are those of _query_boxes."""
-        dev = self.mesh_vertices.device
-        parts = []
-        for name, x in (("origins", origins), ("normals", normals)):
-            if isinstance(x, torch.Tensor):
-                if not x.is_cuda:
-                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
-                if x.device != dev:
-                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
-                                     f"move it or build the intersector on that device")
-            t = _to_device_tensor(x, torch.float32, dev)
-            if t.dim() < 1 or t.shape[-1] != 3:
-                raise ValueError(f"{name} must have shape [*b, 3], got {tuple(t.shape)}")
-            parts.append(t)
-        try:
-            shape = torch.broadcast_shapes(parts[0].shape, parts[1].shape)
-        except RuntimeError:
-            raise ValueError(f"origins of shape {tuple(parts[0].shape)} and normals of shape {tuple(parts[1].shape)} do not broadcast") from None
-        origins, normals = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in parts)
-        return origins, normals, shape[:-1]
-
     def planes_any(self, origins, normals) -> torch.Tensor:
         """bool[*b]: does any triangle meet the plane through `origins` with the normal `normals` -- one launch of
         libtriro_planes.so (tr_planes_any), one wave per plane.  origins and normals are [*b, 3] and broadcast against each
         other; the normal need not be a unit vector.  A triangle MEETS a plane unless its vertices lie strictly on one side,
         touching included (csrc/tr_planes.h has the predicate).  A plane with a NaN, an infinity or a zero normal meets nothing,
         and a triangle with a non-finite coordinate is never met."""
-        origins, normals, b = self._query_planes(origins, normals)
+        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
         return hops.planes_native(self.as_wrapper, origins, normals, "any").reshape(b)
 
     def planes_count(self, origins, normals, cut=False) -> torch.Tensor:
         """int32[*b]: how many triangles meet each plane (tr_planes_count), or with cut=True how many it CUTS: the triangles that
         own a segment of the section; see planes_any and section_segments"""
-        origins, normals, b = self._query_planes(origins, normals)
+        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
         return hops.planes_native(self.as_wrapper, origins, normals, "count", cut).reshape(b)
 
     def faces_on_planes(self, origins, normals, cut=False):
         """(offsets int64[n + 1], tri_idx int32[h]) for the planes flattened in order -- the triangles that meet (cut=True: are
         cut by) plane i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped.  One count launch, one scan, one host read
         of the total to size the outputs, one fill."""
-        origins, normals, b = self._query_planes(origins, normals)
+        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
         offsets, face, _ = hops.faces_on_planes_native(self.as_wrapper, origins, normals, cut)
         return offsets, face
 
@@ -521,7 +500,7 @@ class RayMeshIntersector:
         the positive side.  A crossing point is interpolated from the negative to the positive end of its edge, so the two
         triangles of an edge agree on it bit for bit and the segments of a closed mesh close into loops exactly.  Launches as
         faces_on_planes."""
-        origins, normals, b = self._query_planes(origins, normals)
+        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
         return hops.faces_on_planes_native(self.as_wrapper, origins, normals, True, True)
 
     def section_multiplane(self, origin, normal, heights):
