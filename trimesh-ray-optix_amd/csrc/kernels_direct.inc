@@ -161,7 +161,60 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
     if constexpr (PLAIN) {
         bool l0 = false, l1 = false;       // child 0 / 1 of the lane's last visit is an accepted leaf
         int32_t c0 = 0, c1 = 0;
-        while (trip < steal_min) {
+        // UNIFORM TOP: under an 8x8 pixel tile the first trips of the phase find every visiting lane at the SAME node, from the
+        // root on (headline: 12.7 of a wave's 48 trips, profiles/r11_descent_model.txt), and nearly every tile's rays point
+        // into one octant.  On those trips the record, the children, their leaf flags and the choice of each axis' entry and
+        // exit plane are the same in all 64 lanes: the record is read once through the scalar memory path (a uniform address
+        // in the constant address space, as in tr_fused_step's UNI branch; read only -- every store stays a vector store or an
+        // LDS write) and that work is done once on the scalar unit (tr_uniform_test, tr_uniform_wave), in place of the phase's two 64-lane
+        // gathers of the same 32 bytes, its address shift, six v_perm_b32 and the sign tests on the children.  Per lane the
+        // same fma per plane, the same box test and swap rule, the same push.  The octant test is paid ONCE per wave, against
+        // the first lane that has a ray (lane 0 may have none); a wave that fails it goes straight to the phase.  The loop is
+        // left after the first trip on which a lane accepts a leaf child, the lanes' next nodes differ, a lane has no child
+        // to descend into (it pops here, once, outside the loop: no lane loses its node inside it, so the lanes with a node
+        // are the lanes with `go` throughout) or the trip reaches `steal_min`; it leaves behind what the phase's own trips
+        // would have: node and stack pointer per lane, the last trip's leaf report, the trip count.
+        bool stop = false;                 // wave-uniform: the uniform top ended on a trip that ends the phase as well
+        {
+            const unsigned long long act = __ballot(go);
+            if (act != 0ull && trip < steal_min) {
+                const int first = (int)__builtin_ctzll(act);
+                const uint32_t sn = (uint32_t)__builtin_amdgcn_readlane((int)r.sel_n, first);
+                const uint32_t sf = (uint32_t)__builtin_amdgcn_readlane((int)r.sel_f, first);
+                const uint32_t sz = (uint32_t)__builtin_amdgcn_readlane((int)r.sel_z, first);
+                if (__ballot(go && (r.sel_n != sn || r.sel_f != sf || r.sel_z != sz)) == 0ull) {
+                    const tr_uoctant oct = tr_uniform_octant(sn, sz);
+                    int32_t nu = 0;        // the wave's node
+                    tr_uwave u;
+                    bool more;             // (one condition of bitwise terms, one branch: the short-circuit form is twenty scalar instructions longer)
+#pragma unroll 1
+                    do {
+                        typedef const __attribute__((address_space(4))) int32_t* tr_ci32p;
+                        const tr_ci32p sp = (tr_ci32p)(unsigned long long)tr_qnode_ptr<COMPACT>(b, nu);
+                        tr_i4 w0, w1;
+                        w0.x = sp[0]; w0.y = sp[1]; w0.z = sp[2]; w0.w = sp[3];
+                        w1.x = sp[4]; w1.y = sp[5]; w1.z = sp[6]; w1.w = sp[7];
+                        bool a0, a1, lt;
+                        tr_uniform_test<Q>(r, w0, w1, oct, res, a0, a1, lt);
+                        if (STATS && go) cnt->nodes++;
+                        // (the ballots beside their compares, in front of the push's branch: each IS its compare's result register)
+                        u = tr_uniform_wave(act, __builtin_amdgcn_ballot_w64(a0), __builtin_amdgcn_ballot_w64(a1),
+                                            __builtin_amdgcn_ballot_w64(lt), w1.z, w1.w);
+                        c0 = w1.z; c1 = w1.w;
+                        if (tr_lane_in(u.both, lane)) tr_addr_push(ar, fs.sa, tr_lane_in(u.sw, lane) ? c0 : c1);
+                        TR_CONVERGE();
+                        trip++;
+                        more = ((u.l0 | u.l1 | u.pop) == 0ull) & ((u.sw == 0ull) | (u.sw == act)) & (trip < steal_min);
+                        nu = u.sw != 0ull ? c1 : c0;
+                    } while (more);
+                    l0 = tr_lane_in(u.l0, lane); l1 = tr_lane_in(u.l1, lane);
+                    if (go) fs.node = tr_lane_in(u.sw, lane) ? c1 : c0;
+                    if (tr_lane_in(u.pop, lane)) fs.node = tr_addr_pop(ar, fs.sa);
+                    stop = (u.l0 | u.l1) != 0ull || !TR_WAVE_ANY(fs.node >= 0);
+                }
+            }
+        }
+        if (!stop) while (trip < steal_min) {
             l0 = false; l1 = false;
             if (fs.node >= 0) tr_descent_step<Q, STATS, COMPACT>(b, r, fs, res, cnt, ring, l0, l1, c0, c1);
             TR_CONVERGE();

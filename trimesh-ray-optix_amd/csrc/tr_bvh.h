@@ -1121,6 +1121,87 @@ TR_HD void tr_descent_step(const tr_bvh_view& b, const tr_ray& r, tr_astate& st,
     if (!(h0 || h1)) st.node = tr_addr_pop(ar, st.sa);
 }
 
+// UNIFORM TRIP: tr_descent_step's trip for a wave whose visiting lanes are all at ONE node and whose rays all point into ONE
+// octant.  The record (w0, w1) and the octant are then the same in every lane -- on the device they sit in scalar registers
+// -- and everything that depends on them alone is done once for the wave, on the scalar unit, and in as few instructions as
+// the vector unit saves: the wave pays for every instruction it issues, of either kind (part R17: a first form with
+// 112 scalar instructions per trip was 2 % SLOWER with 4 % fewer vector instructions).  Three pieces, which the kernel
+// (wave_traverse_steal) and the host simulation (tests/host_sim/uniform_top_model.cpp) put together in the same way:
+//   tr_uniform_test   per lane: the box test of both children -- the conversion of each chosen plane (one scalar operand
+//                     each), the same fma((float)q, a, n) per plane as tr_qnode_slabs, the same tr_slab_hit against the same
+//                     cull limit -- as three compares: box 0 / 1 accepted, child 1 nearer;
+//   tr_uniform_wave   per wave, on lane masks (bit k = lane k): from the three compares of every lane (the device's ballots)
+//                     and the children, the lanes that accept a leaf child, push, descend into child 1, have no child to go
+//                     to -- tr_descent_step's formulas, 64 lanes per scalar instruction;
+//   tr_lane_in        a lane's bit of such a mask (on the device the mask IS the condition register: no instruction).
+// The lane's next node is NOT written and its far-child stack is NOT popped inside the loop: the caller goes on to child
+// `sw` while that is the same child for every lane, and leaves the loop -- writing the nodes, popping where `pop` -- after
+// the first trip on which it is not, some lane has no child to go to, or a leaf child is accepted.
+struct tr_uoctant {
+    uint32_t mxy;        // 0xffff in the half of an (x | y << 16) pair whose axis the rays walk in the negative direction
+    uint32_t she, shf;   // shift of the (lo.z | hi.z << 16) pair that brings the entry / the exit plane down
+};
+// from the selectors of any ray of the wave (tr_ray_setup: sel_n, sel_z)
+TR_HD tr_uoctant tr_uniform_octant(uint32_t sel_n, uint32_t sel_z) {
+    const bool nx = (sel_n & 0x0400u) != 0u, ny = (sel_n & 0x04000000u) != 0u, nz = (sel_z & 2u) != 0u;
+    return tr_uoctant{(nx ? 0xffffu : 0u) | (ny ? 0xffff0000u : 0u), nz ? 16u : 0u, nz ? 0u : 16u};
+}
+template <int Q>
+TR_HD void tr_uniform_test(const tr_ray& r, const tr_i4& w0, const tr_i4& w1, const tr_uoctant& oct, const tr_result& res,
+                           bool& a0, bool& a1, bool& lt) {
+    const uint32_t q[6] = {(uint32_t)w0.x, (uint32_t)w0.y, (uint32_t)w0.z, (uint32_t)w0.w, (uint32_t)w1.x, (uint32_t)w1.y};
+    float tn[2], tf[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        // {lo.x, lo.y} and {hi.x, hi.y} with the halves of the negative axes exchanged: {entry x, entry y}, {exit x, exit y}
+        const uint32_t t = (q[3 * c] ^ q[3 * c + 2]) & oct.mxy;
+        const uint32_t e = q[3 * c] ^ t, f = q[3 * c + 2] ^ t, z = q[3 * c + 1];
+        const float ex = (float)(e & 0xffffu), ey = (float)(e >> 16), ez = (float)((z >> oct.she) & 0xffffu);
+        const float fx = (float)(f & 0xffffu), fy = (float)(f >> 16), fz = (float)((z >> oct.shf) & 0xffffu);
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef float tr_v2 __attribute__((ext_vector_type(2)));      // the pairs of tr_qnode_slabs
+        const tr_v2 a = __builtin_elementwise_fma(tr_v2{ex, ey}, tr_v2{r.qax, r.qay}, tr_v2{r.qnx, r.qny});
+        const tr_v2 b = __builtin_elementwise_fma(tr_v2{fx, fy}, tr_v2{r.qax, r.qay}, tr_v2{r.qfx, r.qfy});
+        const tr_v2 d = __builtin_elementwise_fma(tr_v2{ez, fz}, tr_v2{r.qaz, r.qaz2}, tr_v2{r.qnz, r.qfz});
+        tn[c] = fmaxf(fmaxf(a.x, a.y), d.x);
+        tf[c] = fminf(fminf(b.x, b.y), d.y);
+#else
+        tn[c] = fmaxf(fmaxf(fmaf(ex, r.qax, r.qnx), fmaf(ey, r.qay, r.qny)), fmaf(ez, r.qaz, r.qnz));
+        tf[c] = fminf(fminf(fmaf(fx, r.qax, r.qfx), fmaf(fy, r.qay, r.qfy)), fmaf(fz, r.qaz, r.qfz));
+#endif
+    }
+    const float lim = tr_cull_limit<Q>(res);
+    a0 = tr_slab_hit(tn[0], tf[0], lim);
+    a1 = tr_slab_hit(tn[1], tf[1], lim);
+    lt = tn[1] < tn[0];
+}
+struct tr_uwave {
+    uint64_t l0, l1;     // child 0 / 1 is an accepted leaf                     (tr_descent_step: l0, l1)
+    uint64_t both;       // both children are accepted internal nodes: push     (both)
+    uint64_t sw;         // descend into child 1                                (swap; set for a lane of `pop` as well)
+    uint64_t pop;        // no accepted internal child                          (!(h0 || h1))
+};
+// act: the lanes with a node; a0 / a1 / lt: tr_uniform_test's compares of every lane, whatever it computed them from
+TR_HD tr_uwave tr_uniform_wave(uint64_t act, uint64_t a0, uint64_t a1, uint64_t lt, int32_t c0, int32_t c1) {
+    const uint64_t m0 = a0 & act, m1 = a1 & act;
+    const uint64_t h0 = c0 >= 0 ? m0 : 0ull, h1 = c1 >= 0 ? m1 : 0ull;
+    tr_uwave u;
+    u.l0 = m0 ^ h0;
+    u.l1 = m1 ^ h1;
+    u.both = h0 & h1;
+    u.sw = ((u.both & lt) | ~h0) & act;
+    u.pop = act & ~(h0 | h1);
+    return u;
+}
+TR_HD bool tr_lane_in(uint64_t mask, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane;
+    return __builtin_amdgcn_inverse_ballot_w64(mask);
+#else
+    return ((mask >> lane) & 1ull) != 0ull;
+#endif
+}
+
 
 // ---- unordered two-phase schedule (any / count / location) --------------------------------------
 // Queries that do not prune by distance gain nothing from near-first order or from testing a
