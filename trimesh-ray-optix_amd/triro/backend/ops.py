@@ -1438,3 +1438,49 @@ def scene_points_list_native(handle, device_index, points, direction, stack_entr
     count = scene_points_count_native(handle, device_index, points, direction, stack_entries)
     offsets, total = _scan_counts(count)
     return offsets, scene_points_fill_native(handle, device_index, points, direction, count, offsets[:n], total, stack_entries)
+
+
+# --- the nearest placed triangle of a scene (include/triro_scene_nearest.h, csrc/scene_nearest.hip) ------------------------
+SCENE_NEAREST_ABI_VERSION = 1    # TR_SCENE_NEAREST_ABI_VERSION of include/triro_scene_nearest.h
+
+# every symbol include/triro_scene_nearest.h declares: (restype, argtypes)
+SCENE_NEAREST_ABI = {
+    "tr_scene_nearest_abi_version": (_int, []),
+    "tr_scene_nearest_stack_capacity": (_int, []),
+    "tr_scene_closest_point": (_int, [_vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+_scene_nearest = _Satellite("scene_nearest", SCENE_NEAREST_ABI, get_scene_module)   # the scene handles are libtriro_scene.so's
+scene_nearest_library_path = _scene_nearest.path
+get_scene_nearest_module = _scene_nearest.load
+
+
+def scene_closest_point_native(handle, device_index, points, max_distance=None, stack_entries=0, want_closest=True, want_distance=True):
+    """tr_scene_closest_point: (closest float32[n, 3] or None, distance float32[n] or None, instance int32[n], tri int32[n])
+    for float32 points [n, 3] on the scene's GPU: the nearest placed triangle, the instance it belongs to and its face index
+    in the member mesh; (NaN, +Inf, -1, -1) where there is none.  max_distance: None (unbounded), a number, or a dense
+    float32 [n] tensor on that GPU.  stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).
+    Nothing is allocated by the library and nothing is synchronised."""
+    _check_points(points)
+    if points.device.index != device_index:
+        raise ValueError(f"points are on {points.device} but the scene lives on cuda:{device_index}; move the points")
+    lib = get_scene_nearest_module()
+    dev, n = points.device, points.shape[0]
+    points = points.contiguous()
+    rptr, r = None, float("inf")
+    if isinstance(max_distance, torch.Tensor):
+        if not max_distance.is_cuda or max_distance.device != dev or max_distance.dtype != torch.float32 or \
+                tuple(max_distance.shape) != (n,) or not max_distance.is_contiguous():
+            raise ValueError(f"max_distance must be a number or a contiguous float32 tensor of {n} elements on the points' device")
+        rptr = max_distance.data_ptr()
+    elif max_distance is not None:
+        r = C.c_float(float(max_distance)).value      # rounded to float32 (beyond its range: +Inf, as a float32 tensor would hold it)
+    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
+    distance = _new_output((n,), torch.float32, dev) if want_distance else None
+    inst = _new_output((n,), torch.int32, dev)
+    tri = _new_output((n,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib.tr_scene_closest_point(handle, points.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), inst.data_ptr(),
+                                          tri.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    return closest, distance, inst, tri

@@ -192,3 +192,29 @@ class RaySceneIntersector:
         read of the total to size the output, one fill."""
         flat, direction, _ = self._points(points, check_direction)
         return hops.scene_points_list_native(self._handle, self.device.index, flat, direction)
+
+    # -- the nearest placed triangle (libtriro_scene_nearest.so, include/triro_scene_nearest.h) ------------------------------
+    def closest_point(self, points, max_distance=None):
+        """(closest[*b,3] float32, distance[*b] float32, instance[*b] int32, triangle_id[*b] int32) of points [*b, 3]: the
+        nearest placed triangle over all instances, one launch (tr_scene_closest_point).  The members' hierarchies are walked
+        as they are; boxes and triangles are placed into world space by the scene's own float32 chain and measured there in
+        float64, so the answer is RayMeshIntersector.closest_point on the mesh that bakes every placed copy, bit for bit,
+        without baking.  Among triangles at exactly the same distance the smaller (instance, face index) wins;
+        triangle_id is the face index in the member mesh, closest is in world space.  A placed triangle with a non-finite
+        coordinate is never returned.  A point with a non-finite component, a scene without a usable instance:
+        (NaN, +Inf, -1, -1).
+
+        max_distance (a number or a tensor that broadcasts to the batch shape; None: unbounded): the nearest placed triangle
+        within that distance or none.  A triangle at exactly max_distance is within; NaN or negative: (NaN, +Inf, -1, -1)."""
+        flat, b = self._helper._proximity_points(points)
+        r = None if max_distance is None else self._helper._proximity_radius(max_distance, b, "max_distance")
+        closest, distance, inst, tri = hops.scene_closest_point_native(self._handle, self.device.index, flat, r)
+        return closest.reshape(*b, 3), distance.reshape(b), inst.reshape(b), tri.reshape(b)
+
+    def signed_distance(self, points, check_direction=None) -> torch.Tensor:
+        """float32[*b]: closest_point's distance with the sign of contains_points -- POSITIVE inside any placed copy, negative
+        elsewhere (trimesh's convention, as RayMeshIntersector.signed_distance).  `check_direction` is contains_points'."""
+        flat, direction, b = self._points(points, check_direction)
+        _, distance, _, _ = hops.scene_closest_point_native(self._handle, self.device.index, flat, None, want_closest=False)
+        inside = hops.scene_points_any_native(self._handle, self.device.index, flat, direction)
+        return torch.where(inside, distance, -distance).reshape(b)
