@@ -74,9 +74,9 @@ def test_abi_version_and_stack_capacity_match_the_sources():
         res, args = hops.BOXES_ABI[name]
         assert len(args) == nargs and args[3] is ctypes.c_int64 and args[-2] is ctypes.c_int, name
     assert hops.BOXES_ABI["tr_boxes_fill"][1][6] is ctypes.c_int64
-    # the row limit and the ordering are tr_within.h's, included and not copied
-    assert '#include "tr_within.h"' in core and "tr_within_sort(" in core and "tr_within_limit(" in core
-    assert not re.search(r"\btr_within_(sort|limit|sift|swap)\s*\([^;{]*\)\s*\{", core)
+    # the row limit and the ordering are tr_walk.h's / tr_within.h's, included and not copied
+    assert '#include "tr_within.h"' in core and "tr_within_sort(" in core and "tr_rows_limit(" in core
+    assert not re.search(r"\btr_(within_sort|rows_limit|rows_sift|rows_sort|walk_push|walk_pop)\s*\([^;{]*\)\s*\{", core)
 
 
 def test_the_other_libraries_gained_no_symbol():

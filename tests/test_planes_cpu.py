@@ -72,8 +72,8 @@ def test_abi_version_and_frontier_capacity_match_the_sources():
         assert len(args) == nargs and args[3] is ctypes.c_int64 and args[-2] is ctypes.c_int and args[-3] is ctypes.c_int, name
     assert hops.PLANES_ABI["tr_planes_fill"][1][6] is ctypes.c_int64
     # the row limit and the activity rule are tr_within.h's / tr_nearest.h's, included and not copied
-    assert '#include "tr_within.h"' in core and "tr_within_limit(" in open(os.path.join(ROOT, "trimesh-ray-optix_amd", "csrc", "planes.hip")).read()
-    assert "tr_near_active(" in core and not re.search(r"\btr_(within_limit|near_active)\s*\([^;{]*\)\s*\{", core)
+    assert '#include "tr_within.h"' in core and "tr_rows_limit(" in open(os.path.join(ROOT, "trimesh-ray-optix_amd", "csrc", "planes.hip")).read()
+    assert "tr_near_active(" in core and not re.search(r"\btr_(rows_limit|near_active)\s*\([^;{]*\)\s*\{", core)
 
 
 def test_the_other_libraries_gained_no_symbol():

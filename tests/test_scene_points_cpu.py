@@ -88,7 +88,7 @@ def test_abi_version_stack_capacity_and_the_public_methods():
     # the header composes the contracts and restates none; the .hip file reads the one definition of the handle
     core = open(os.path.join(CSRC, "tr_scene_points.h")).read()
     assert '#include "tr_scene_cross.h"' in core and '#include "tr_points.h"' in core
-    assert "tr_point_decide(" in core and "tr_scene_ray(" in core and "tr_cross_rewalk<" in core and "tr_cross_visit<" in core
+    assert "tr_point_decide(" in core and "tr_scene_ray(" in core and "tr_cross_probe<" in core and "tr_cross_visit<" in core
     src = open(os.path.join(CSRC, "scene_points.hip")).read()
     assert '#include "tr_scene_handle.h"' in src and not re.search(r"^struct tr_scene \{", src, re.M)
     assert "hipMalloc" not in src and "Synchronize" not in src and "hipMemset" not in src

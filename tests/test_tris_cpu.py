@@ -77,9 +77,9 @@ def test_abi_version_and_stack_capacity_match_the_sources():
     assert hops.TRIS_ABI["tr_tris_fill"][1][5] is ctypes.c_int64
     # the culling, the activity rule, the row limit and the ordering are included and not copied
     assert '#include "tr_boxes.h"' in core
-    for used in ("tr_within_sort(", "tr_within_limit(", "tr_within_push(", "tr_within_pop(", "tr_boxes_load(", "tr_near_active(", "tr_load_tri<"):
+    for used in ("tr_within_sort(", "tr_rows_limit(", "tr_set_probe<", "tr_set_query(", "tr_set_kernel<", "tr_near_active(", "tr_load_tri<"):
         assert used in core + open(os.path.join(ROOT, "trimesh-ray-optix_amd", "csrc", "tris.hip")).read(), used
-    assert not re.search(r"^TR_HD\w*\s+[\w:<>&* ]+\btr_(within|boxes?|near|load)_\w+\s*\(", core, re.M)      # no definition of theirs
+    assert not re.search(r"^TR_HD\w*\s+[\w:<>&* ]+\btr_(within|boxes?|near|load|walk|rows|set)_\w+\s*\(", core, re.M)      # no definition of theirs
 
 
 def test_the_other_libraries_gained_no_symbol():

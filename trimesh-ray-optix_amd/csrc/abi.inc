@@ -133,7 +133,7 @@ int tr_device_topology(int device, tr_topology* out) {
     tr_device_state* st;
     TR_TRY(tr_get_device_state(device, &st));
     tr_device_guard guard;
-    if (guard.enter(device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, device));
     tr_policy_units(st);
     out->num_cus = st->num_cus; out->num_xcd = st->num_xcd; out->waves_per_cu = st->waves_per_cu; out->reserved = 0;
     out->l2_bytes = st->l2_bytes;
@@ -190,7 +190,7 @@ int tr_intersects_location_fill(const tr_bvh* bvh, const tr_rays* rays, int32_t 
     if (!d_offsets) return tr_fail(TR_ERR_INVALID_ARG, "d_offsets == NULL");
     tr_device_guard guard;
     TR_TRY(enter_bvh_device(bvh, rays, &guard));
-    tr_bvh_view view = make_view(bvh);
+    tr_bvh_view view = tr_view_of(bvh);
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)((rf.n + 255) / 256)), block(256);
     if (cap <= 8)
@@ -226,7 +226,7 @@ int tr_location_fill_slots(const tr_bvh* bvh, const tr_rays* rays, int32_t cap, 
     if (!d_count || !d_offsets || !d_hits) return tr_fail(TR_ERR_INVALID_ARG, "null input pointer");
     tr_device_guard guard;
     TR_TRY(enter_bvh_device(bvh, rays, &guard));
-    tr_bvh_view view = make_view(bvh);
+    tr_bvh_view view = tr_view_of(bvh);
     const int64_t threads = rf.n * cap;
     hipLaunchKernelGGL(k_fill_list, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        view, rf, cap, d_count, d_offsets, d_hits, d_loc, d_ray_idx, d_tri_idx, ray_base);

@@ -1,7 +1,8 @@
 // boxes.hip -- libtriro_boxes.so (include/triro_boxes.h): the faces that meet each axis-aligned box.
 //
-// The contract, the culling proof and the walk are csrc/tr_boxes.h (host + device) on the stack, the row limit and the
-// ordering of csrc/tr_within.h; this file is the wave loop around tr_boxes_visit, the launches and the C entries.
+// The contract, the culling proof and the walk are csrc/tr_boxes.h (host + device) on the stack and the row limit of
+// csrc/tr_walk.h and the ordering of csrc/tr_within.h; this file is the wave loop around tr_boxes_visit, the launches and the
+// C entries.
 //
 //  * One box per lane, block k takes boxes 128 k ... 128 k + 127 (64-bit index math), shaped like k_within.
 //  * k_boxes<ANY | COUNT | FILL>: the stack of a lane is a column of LDS, TR_BOXES_STACK = 32 node ids, 16 KB per
@@ -16,7 +17,7 @@
 
 namespace {
 
-constexpr int BX_BS = 128;      // one box per lane, two waves per workgroup
+constexpr int BX_BS = TR_LANE_BS;      // one box per lane, two waves per workgroup
 
 struct bx_query {
     tr_box q;
@@ -39,7 +40,7 @@ __device__ __forceinline__ bx_query bx_load(const tr_bvh_view& b, const float* _
 }  // namespace
 
 // ANY: out8[i] = 0 / 1.  COUNT: out32[i] = the number of faces met.  FILL: the keys (tr_boxes_key) of the faces of box i, in
-// walk order, at rows offsets[i] .. of face, at most tr_within_limit of them.
+// walk order, at rows offsets[i] .. of face, at most tr_rows_limit of them.
 template <int MODE>
 __global__ __launch_bounds__(BX_BS) void k_boxes(tr_bvh_view b, const float* __restrict__ lo, const float* __restrict__ hi, int64_t n,
                                                  uint8_t* __restrict__ out8, int32_t* __restrict__ out32,
@@ -54,20 +55,20 @@ __global__ __launch_bounds__(BX_BS) void k_boxes(tr_bvh_view b, const float* __r
     acc.count = 0; acc.limit = 0; acc.key = nullptr;
     if (MODE == TR_BOXES_FILL && q.in_range) {
         const int64_t off = offsets[i];
-        acc.limit = tr_within_limit(count[i], off, total);
+        acc.limit = tr_rows_limit(count[i], off, total);
         if (acc.limit > 0) acc.key = face + off;
     }
-    const bool walk = q.valid && !tr_boxes_full<MODE>(acc);      // (FILL: a box without rows has nothing to do)
+    const bool walk = q.valid && !tr_set_full<MODE>(acc);      // (FILL: a box without rows has nothing to do)
     if (b.num_tris >= 2) {      // (wave-uniform)
         const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_BOXES_STACK);
-        tr_within_state st;
+        tr_walk_state st;
         st.node = walk ? 0 : -1; st.sp = 0;
         for (;;) {
             if (!TR_WAVE_ANY(st.node >= 0)) break;
             if (st.node >= 0) tr_boxes_visit<MODE>(b, q.q, st, acc, stack, cap2);
             TR_CONVERGE();
         }
-        if (tr_within_lost(st.sp) && !tr_boxes_full<MODE>(acc)) {      // cold: the partial result is dropped, not added to
+        if (tr_walk_lost(st.sp) && !tr_set_full<MODE>(acc)) {      // cold: the partial result is dropped, not added to
             acc.count = 0;
             tr_boxes_rewalk<MODE>(b, q.q, acc);
         }
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(BX_BS) void k_boxes_rows(int64_t n, const int32_t* 
     const int64_t i = (int64_t)blockIdx.x * BX_BS + threadIdx.x;
     if (i >= n) return;
     const int64_t off = offsets[i];
-    const int32_t m = tr_within_limit(count[i], off, total);
+    const int32_t m = tr_rows_limit(count[i], off, total);
     if (m <= 0) return;
     tr_boxes_rows(face + off, inside ? inside + off : nullptr, m);
 }
@@ -96,27 +97,13 @@ namespace {
 // the checks every entry shares; nblocks comes back
 int bx_check(const tr_bvh* bvh, const float* d_lo, const float* d_hi, int64_t n, const void* d_required, int stack_entries,
              int64_t& nblocks) {
-    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
-    if (n < 0) return tr_fail(TR_ERR_INVALID_ARG, "n < 0");
-    if (stack_entries < 0 || stack_entries > TR_BOXES_STACK)
-        return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_BOXES_STACK));
-    if (n > 0 && (!d_lo || !d_hi || !d_required)) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
-    nblocks = (n + BX_BS - 1) / BX_BS;
-    if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many boxes for one launch");
-    return TR_OK;
-}
-
-tr_bvh_view bx_view(const tr_bvh* bvh) {
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    return view;
+    return tr_lane_check(bvh, d_lo && d_hi, n, d_required, stack_entries, TR_BOXES_STACK, "boxes", nblocks);
 }
 
 template <int MODE>
 int bx_launch(const tr_bvh* bvh, const float* d_lo, const float* d_hi, int64_t n, uint8_t* out8, int32_t* out32, const int32_t* d_count,
               const int64_t* d_offsets, int64_t total, int32_t* d_face, int stack_entries, int64_t nblocks, void* stream) {
-    hipLaunchKernelGGL(k_boxes<MODE>, dim3((unsigned)nblocks), dim3(BX_BS), 0, (hipStream_t)stream, bx_view(bvh), d_lo, d_hi, n, out8,
+    hipLaunchKernelGGL(k_boxes<MODE>, dim3((unsigned)nblocks), dim3(BX_BS), 0, (hipStream_t)stream, tr_view_of(bvh), d_lo, d_hi, n, out8,
                        out32, d_count, d_offsets, total, d_face, stack_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;
@@ -135,7 +122,7 @@ int tr_boxes_any(const tr_bvh* bvh, const float* d_lo, const float* d_hi, int64_
     if (int rc = bx_check(bvh, d_lo, d_hi, n, d_any, stack_entries, nblocks)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return bx_launch<TR_BOXES_ANY>(bvh, d_lo, d_hi, n, d_any, nullptr, nullptr, nullptr, 0, nullptr, stack_entries, nblocks, stream);
 }
 
@@ -144,7 +131,7 @@ int tr_boxes_count(const tr_bvh* bvh, const float* d_lo, const float* d_hi, int6
     if (int rc = bx_check(bvh, d_lo, d_hi, n, d_count, stack_entries, nblocks)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return bx_launch<TR_BOXES_COUNT>(bvh, d_lo, d_hi, n, nullptr, d_count, nullptr, nullptr, 0, nullptr, stack_entries, nblocks, stream);
 }
 
@@ -152,12 +139,10 @@ int tr_boxes_fill(const tr_bvh* bvh, const float* d_lo, const float* d_hi, int64
                   int64_t total, int32_t* d_face, uint8_t* d_inside, int stack_entries, void* stream) {
     int64_t nblocks = 0;
     if (int rc = bx_check(bvh, d_lo, d_hi, n, d_count, stack_entries, nblocks)) return rc;
-    if (total < 0) return tr_fail(TR_ERR_INVALID_ARG, "total < 0");
-    if (n > 0 && !d_offsets) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
-    if (n > 0 && total > 0 && !d_face) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument (d_face)");
+    TR_TRY(tr_fill_check(n, total, d_offsets, d_face != nullptr, "null pointer argument (d_face)"));
     if (n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     if (int rc = bx_launch<TR_BOXES_FILL>(bvh, d_lo, d_hi, n, nullptr, nullptr, d_count, d_offsets, total, d_face, stack_entries, nblocks,
                                           stream))
         return rc;

@@ -10,7 +10,7 @@
 //  * Rays arrive as tr_rays and are read as every other kernel reads them: RayFetch / fetch_ray of kernels_common.inc
 //    (dense, broadcast and general strides).
 //  * k_cross<COUNT | FILL>: the stack of a lane is a column of LDS, TR_CROSS_STACK = 32 node ids, 16 KB per workgroup.  A
-//    lane whose stack overflowed drops what it found and walks the tree again without one (tr_cross_rewalk) after the wave's
+//    lane whose stack overflowed drops what it found and walks the tree again without one (tr_rewalk on a tr_cross_probe) after the wave's
 //    loop.  FILL leaves the rows of a ray in walk order; k_cross_rows (no LDS) orders them by (t, face) and evaluates the
 //    optional front / loc / uv / ray rows.
 #include <string>
@@ -50,7 +50,7 @@ __device__ __forceinline__ cr_query cr_load(const tr_bvh_view& b, const RayFetch
 }  // namespace
 
 // COUNT: out32[i] = the number of crossings.  FILL: the crossings of ray i, in walk order, at rows offsets[i] .. of face and t
-// (and their arena slots at the same rows of slot, where given), at most tr_cross_limit of them.
+// (and their arena slots at the same rows of slot, where given), at most tr_rows_limit of them.
 template <int MODE>
 __global__ __launch_bounds__(CR_BS) void k_cross(tr_bvh_view b, RayFetch rf, const float* __restrict__ tmin,
                                                  const float* __restrict__ tmax, int32_t* __restrict__ out32,
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(CR_BS) void k_cross(tr_bvh_view b, RayFetch rf, con
     acc.count = 0; acc.limit = 0; acc.face = nullptr; acc.t = nullptr; acc.slot = nullptr;
     if (MODE == TR_CROSS_FILL && q.in_range) {
         const int64_t off = offsets[i];
-        acc.limit = tr_cross_limit(count[i], off, total);
+        acc.limit = tr_rows_limit(count[i], off, total);
         if (acc.limit > 0) { acc.face = face + off; acc.t = t + off; acc.slot = slot ? slot + off : nullptr; }
     }
     const bool walk = q.valid && !tr_cross_full<MODE>(acc);      // (FILL: a ray without rows has nothing to do)
@@ -78,9 +78,9 @@ __global__ __launch_bounds__(CR_BS) void k_cross(tr_bvh_view b, RayFetch rf, con
             if (st.node >= 0) tr_cross_visit<MODE>(b, q.r, q.lo, q.hi, st, acc, stack, cap2);
             TR_CONVERGE();
         }
-        if (tr_cross_lost(st.sp) && !tr_cross_full<MODE>(acc)) {      // cold: the partial result is dropped, not added to
+        if (tr_walk_lost(st.sp) && !tr_cross_full<MODE>(acc)) {      // cold: the partial result is dropped, not added to
             acc.count = 0;
-            tr_cross_rewalk<MODE>(b, q.r, q.lo, q.hi, acc);
+            tr_rewalk(b, tr_cross_probe<MODE>{b, q.r, q.lo, q.hi, acc});
         }
     } else if (walk) {
         tr_counters* nc = nullptr;
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(CR_BS) void k_cross_rows(tr_bvh_view b, RayFetch rf
     const int64_t i = (int64_t)blockIdx.x * CR_BS + threadIdx.x;
     if (i >= rf.n) return;
     const int64_t off = offsets[i];
-    const int32_t m = tr_cross_limit(count[i], off, total);
+    const int32_t m = tr_rows_limit(count[i], off, total);
     if (m <= 0) return;
     float o[3], d[3];
     fetch_ray(rf, i, o, d);
@@ -113,62 +113,16 @@ __global__ __launch_bounds__(CR_BS) void k_cross_rows(tr_bvh_view b, RayFetch rf
 
 namespace {
 
-// tr_rays -> RayFetch: the checks and the stride classes of the other entries (range.hip, range_fetch)
-int cross_fetch(const tr_rays* rays, RayFetch* rf) {
-    if (!rays) return tr_fail(TR_ERR_INVALID_ARG, "rays == NULL");
-    if (rays->nray < 0) return tr_fail(TR_ERR_INVALID_ARG, "nray < 0");
-    if (rays->shape[3] != 3) return tr_fail(TR_ERR_INVALID_ARG, "last ray dimension must be 3");
-    int64_t prod = 1;
-    for (int k = 0; k < 3; k++) {
-        const int64_t s = rays->shape[k];
-        if (s == INT64_MAX) continue;
-        if (s < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative ray dimension");
-        prod *= s;
-    }
-    if (prod != rays->nray) return tr_fail(TR_ERR_INVALID_ARG, "nray != product of leading dims");
-    if (rays->nray > 0 && (!rays->d_origins || !rays->d_directions)) return tr_fail(TR_ERR_INVALID_ARG, "null ray pointer");
-    rf->o = rays->d_origins; rf->d = rays->d_directions; rf->n = rays->nray;
-    rf->s0 = rays->shape[0]; rf->s1 = rays->shape[1]; rf->s2 = rays->shape[2];
-    auto classify = [&](const int64_t* st) {
-        bool bcast = true, dense = st[3] == 1;
-        int64_t expect = 3;
-        for (int k = 2; k >= 0; k--) {
-            const int64_t s = rays->shape[k];
-            if (s == INT64_MAX || s == 1) continue;
-            if (st[k] != 0) bcast = false;
-            if (st[k] != expect) dense = false;
-            expect *= s;
-        }
-        return dense ? 0 : (bcast ? 1 : 2);
-    };
-    for (int k = 0; k < 4; k++) { rf->os[k] = rays->ostride[k]; rf->ds[k] = rays->dstride[k]; }
-    rf->omode = classify(rays->ostride);
-    rf->dmode = classify(rays->dstride);
-    rf->aframe = nullptr;
-    if (rf->s0 == INT64_MAX) rf->s0 = 1;
-    if (rf->s1 == INT64_MAX) rf->s1 = 1;
-    if (rf->s2 == INT64_MAX) rf->s2 = 1;
-    if (rf->s0 == 0 || rf->s1 == 0 || rf->s2 == 0) { rf->s0 = rf->s1 = rf->s2 = 1; }
-    return TR_OK;
-}
-
 // the checks every entry shares (what range_launch refuses); the RayFetch and nblocks come back
 int cross_check(const tr_bvh* bvh, const tr_rays* rays, const void* required, int stack_entries, RayFetch& rf, int64_t& nblocks) {
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
-    TR_TRY(cross_fetch(rays, &rf));
+    TR_TRY(make_fetch(rays, &rf));
     if (stack_entries < 0 || stack_entries > TR_CROSS_STACK)
         return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_CROSS_STACK));
     if (rf.n > 0 && !required) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
     nblocks = (rf.n + CR_BS - 1) / CR_BS;
     if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many rays for one launch");
     return TR_OK;
-}
-
-tr_bvh_view cross_view(const tr_bvh* bvh) {
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    return view;
 }
 
 }  // namespace
@@ -186,8 +140,8 @@ int tr_cross_count(const tr_bvh* bvh, const tr_rays* rays, const float* d_tmin, 
     if (int rc = cross_check(bvh, rays, d_count, stack_entries, rf, nblocks)) return rc;
     if (rf.n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
-    hipLaunchKernelGGL((k_cross<TR_CROSS_COUNT>), dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, cross_view(bvh), rf,
+    TR_TRY(tr_enter_device(&guard, bvh->device));
+    hipLaunchKernelGGL((k_cross<TR_CROSS_COUNT>), dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, tr_view_of(bvh), rf,
                        d_tmin, d_tmax, d_count, nullptr, nullptr, (int64_t)0, nullptr, nullptr, nullptr, stack_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;
@@ -206,12 +160,12 @@ int tr_cross_fill(const tr_bvh* bvh, const tr_rays* rays, const float* d_tmin, c
         return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument (d_face, d_t, or d_slot with d_front / d_loc3 / d_uv2)");
     if (rf.n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     if (!evaluate) d_slot = nullptr;
-    hipLaunchKernelGGL((k_cross<TR_CROSS_FILL>), dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, cross_view(bvh), rf,
+    hipLaunchKernelGGL((k_cross<TR_CROSS_FILL>), dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, tr_view_of(bvh), rf,
                        d_tmin, d_tmax, nullptr, d_count, d_offsets, total, d_face, d_t, d_slot, stack_entries);
     TR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cross_rows, dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, cross_view(bvh), rf, d_count, d_offsets,
+    hipLaunchKernelGGL(k_cross_rows, dim3((unsigned)nblocks), dim3(CR_BS), 0, (hipStream_t)stream, tr_view_of(bvh), rf, d_count, d_offsets,
                        total, d_face, d_t, d_slot, d_front, d_loc3, d_uv2, d_ray, ray_base);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;

@@ -1,60 +1,14 @@
-// launch_policy.inc -- included by traverse.hip inside its anonymous namespace: the HOST side of a query -- ray
-// marshaling, device checks, the per-(handle, stream) scheduling state (learned launch order, node-flavour tuner), and
-// launch_query: which launch shape a batch gets and why.
+// launch_policy.inc -- included by traverse.hip inside its anonymous namespace: the HOST side of a query -- device
+// checks, the per-(handle, stream) scheduling state (learned launch order, node-flavour tuner), and launch_query: which
+// launch shape a batch gets and why.  (Ray marshaling: make_fetch, kernels_common.inc.)
 // ---- host side ----------------------------------------------------------------------------------
-int make_fetch(const tr_rays* rays, RayFetch* rf) {
-    if (!rays) return tr_fail(TR_ERR_INVALID_ARG, "rays == NULL");
-    if (rays->nray < 0) return tr_fail(TR_ERR_INVALID_ARG, "nray < 0");
-    if (rays->shape[3] != 3) return tr_fail(TR_ERR_INVALID_ARG, "last ray dimension must be 3");
-    int64_t prod = 1;
-    for (int k = 0; k < 3; k++) {
-        int64_t s = rays->shape[k];
-        if (s == INT64_MAX) continue;
-        if (s < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative ray dimension");
-        prod *= s;
-    }
-    if (prod != rays->nray) return tr_fail(TR_ERR_INVALID_ARG, "nray != product of leading dims");
-    if (rays->nray > 0 && (!rays->d_origins || !rays->d_directions))
-        return tr_fail(TR_ERR_INVALID_ARG, "null ray pointer");
-    rf->o = rays->d_origins; rf->d = rays->d_directions; rf->n = rays->nray;
-    rf->s0 = rays->shape[0]; rf->s1 = rays->shape[1]; rf->s2 = rays->shape[2];
-    auto classify = [&](const int64_t* st) {
-        bool bcast = true, dense = st[3] == 1;
-        int64_t expect = 3;
-        for (int k = 2; k >= 0; k--) {
-            int64_t s = rays->shape[k];
-            if (s == INT64_MAX || s == 1) continue;
-            if (st[k] != 0) bcast = false;
-            if (st[k] != expect) dense = false;
-            expect *= s;
-        }
-        return dense ? 0 : (bcast ? 1 : 2);
-    };
-    for (int k = 0; k < 4; k++) { rf->os[k] = rays->ostride[k]; rf->ds[k] = rays->dstride[k]; }
-    rf->omode = classify(rays->ostride);
-    rf->dmode = classify(rays->dstride);
-    rf->aframe = nullptr;      // no anchoring unless a caller sets the frame (tr_closest_from_slots)
-    if (rf->s0 == INT64_MAX) rf->s0 = 1;   // keep the general path's divisions cheap and safe
-    if (rf->s1 == INT64_MAX) rf->s1 = 1;
-    if (rf->s2 == INT64_MAX) rf->s2 = 1;
-    if (rf->s0 == 0 || rf->s1 == 0 || rf->s2 == 0) { rf->s0 = rf->s1 = rf->s2 = 1; }
-    return TR_OK;
-}
-
-tr_bvh_view make_view(const tr_bvh* bvh) {
-    tr_bvh_view v;
-    v.nodes = bvh->nodes; v.links = bvh->links; v.tris = bvh->tris; v.num_tris = bvh->num_tris;
-    v.qnodes = bvh->qnodes; v.frame = bvh->frame; v.frame_dev = bvh->frame_dev;
-    return v;
-}
-
 // Every query runs on the device that owns the BVH arena, whatever device is current in the
 // calling thread (tr_device_guard restores it), and refuses rays that live on another GPU:
 // the kernel would dereference them (or the arena) across devices -- a memory fault that kills
 // the process, or silent peer traffic.  The pointer query is skipped when the caller is already
 // on the handle's device (the common, checked-by-the-binding case costs nothing extra).
 int enter_bvh_device(const tr_bvh* bvh, const tr_rays* rays, tr_device_guard* guard) {
-    if (guard->enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(guard, bvh->device));
     if (guard->changed && rays && rays->nray > 0) {
         for (const float* p : {rays->d_origins, rays->d_directions}) {
             hipPointerAttribute_t attr;
@@ -707,7 +661,7 @@ int launch_query(const tr_bvh* bvh, const tr_rays* rays, const QueryOut& out,
     tr_device_state* st;
     TR_TRY(tr_get_device_state(bvh->device, &st));
     tr_policy_units(st);
-    const tr_bvh_view view = make_view(bvh);
+    const tr_bvh_view view = tr_view_of(bvh);
     const tr_options opt = tr_opts();   // one snapshot per call
     // 32-bit offsets when both arrays are below 4 GiB; 32-bit trail words when the hierarchy is at most 32 levels high
     // (`compact` = both, `deep` = offsets only).  The instrumented launches (STATS) exist in the generic addressing only.

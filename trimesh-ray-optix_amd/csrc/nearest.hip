@@ -7,7 +7,7 @@
 //  * One point per lane, block k takes points 128 k ... 128 k + 127 (64-bit index math).  No stealing, no learned launch
 //    order, no grid nodes: the walk reads the exact 64-byte nodes (tr_node) and the triangle records.
 //  * The far-child stack of a lane is a column of LDS: TR_NEAR_STACK = 32 entries of {node, float32 bound}, 32 KB per
-//    workgroup.  A lane whose stack overflowed walks the tree again without one (tr_near_rewalk) after the wave's loop.
+//    workgroup.  A lane whose stack overflowed walks the tree again without one (tr_rewalk on a tr_near_probe) after the wave's loop.
 //  * One instantiation, 64-bit address arithmetic.
 #include <string>
 
@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int NR_BS = 128;      // one point per lane, two waves per workgroup
+constexpr int NR_BS = TR_LANE_BS;      // one point per lane, two waves per workgroup
 
 }  // namespace
 
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(NR_BS) void k_closest_point(tr_bvh_view b, const fl
             if (st.node >= 0) tr_near_visit(b, px, py, pz, st, best, stack, cap2);
             TR_CONVERGE();
         }
-        if (tr_near_lost(st.sp)) tr_near_rewalk(b, px, py, pz, best);
+        if (tr_near_lost(st.sp)) tr_rewalk(b, tr_near_probe{b, px, py, pz, best});
     } else if (valid) {
         tr_near_leaf(b, 0, px, py, pz, best);      // no hierarchy below two triangles
     }
@@ -65,20 +65,12 @@ int tr_nearest_stack_capacity(void) { return TR_NEAR_STACK; }
 
 int tr_closest_point(const tr_bvh* bvh, const float* d_points, int64_t n, float* d_closest, float* d_distance, int32_t* d_tri,
                      int stack_entries, void* stream) {
-    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
-    if (n < 0) return tr_fail(TR_ERR_INVALID_ARG, "n < 0");
-    if (stack_entries < 0 || stack_entries > TR_NEAR_STACK)
-        return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_NEAR_STACK));
-    if (n > 0 && (!d_points || !d_tri)) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
-    const int64_t nblocks = (n + NR_BS - 1) / NR_BS;
-    if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many points for one launch");
+    int64_t nblocks = 0;
+    TR_TRY(tr_lane_check(bvh, d_points != nullptr, n, d_tri, stack_entries, TR_NEAR_STACK, "points", nblocks));
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    hipLaunchKernelGGL(k_closest_point, dim3((unsigned)nblocks), dim3(NR_BS), 0, (hipStream_t)stream, view, d_points, n,
+    TR_TRY(tr_enter_device(&guard, bvh->device));
+    hipLaunchKernelGGL(k_closest_point, dim3((unsigned)nblocks), dim3(NR_BS), 0, (hipStream_t)stream, tr_view_of(bvh), d_points, n,
                        d_closest, d_distance, d_tri, stack_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;

@@ -59,7 +59,7 @@ __device__ __forceinline__ int32_t pl_record(const tr_bvh_view& b, const tr_plan
 }  // namespace
 
 // ANY: out8[i] = 0 / 1.  COUNT: out32[i] = the number of faces met (cut).  FILL: the faces of plane i, in walk order, at rows
-// offsets[i] .. of face, at most tr_within_limit of them; with seg, the arena slot of a row in the first word of its segment.
+// offsets[i] .. of face, at most tr_rows_limit of them; with seg, the arena slot of a row in the first word of its segment.
 template <int MODE>
 __global__ __launch_bounds__(TR_PLANES_WAVE) void k_planes(tr_bvh_view b, const float* __restrict__ org, const float* __restrict__ nrm,
                                                            uint8_t* __restrict__ out8, int32_t* __restrict__ out32,
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(TR_PLANES_WAVE) void k_planes(tr_bvh_view b, const 
     int64_t off = 0;
     if (MODE == TR_PLANES_FILL) {
         off = offsets[i];
-        limit = tr_within_limit(count[i], off, total);
+        limit = tr_rows_limit(count[i], off, total);
     }
     int32_t cursor = 0;      // faces found so far (wave-uniform)
     const pl_rows rows = {face, seg, off, limit};
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(PL_ROWS_BS) void k_planes_rows(const int32_t* __res
     __shared__ int32_t ride[PL_TILE];
     const int64_t i = (int64_t)blockIdx.x;
     const int64_t off = offsets[i];
-    const uint32_t m = (uint32_t)tr_within_limit(count[i], off, total);      // (uniform in the workgroup)
+    const uint32_t m = (uint32_t)tr_rows_limit(count[i], off, total);      // (uniform in the workgroup)
     if (m < 2u) return;
     int32_t* f = face + off;
     int32_t* s = seg ? seg + 6 * off : nullptr;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(PL_ROWS_BS) void k_planes_segments(tr_bvh_view b, c
     if (r >= total || b.num_tris <= 0) return;
     const int64_t i = tr_planes_owner(offsets, n, r);
     const int64_t off = offsets[i];
-    const int32_t m = tr_within_limit(count[i], off, total);
+    const int32_t m = tr_rows_limit(count[i], off, total);
     if (r < off || r >= off + m) return;      // (a row between the planes' rows: counts and offsets that are not a scan)
     const int32_t slot = reinterpret_cast<const int32_t*>(seg)[6 * r];
     tr_planes_row(b, pl_load(org, nrm, i), slot, seg + 6 * r);
@@ -194,17 +194,10 @@ int pl_check(const tr_bvh* bvh, const float* d_org, const float* d_nrm, int64_t 
     return TR_OK;
 }
 
-tr_bvh_view pl_view(const tr_bvh* bvh) {
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    return view;
-}
-
 template <int MODE>
 int pl_launch(const tr_bvh* bvh, const float* d_org, const float* d_nrm, int64_t n, uint8_t* out8, int32_t* out32, const int32_t* d_count,
               const int64_t* d_offsets, int64_t total, int32_t* d_face, float* d_segments, int cut, int frontier_entries, void* stream) {
-    hipLaunchKernelGGL(k_planes<MODE>, dim3((unsigned)n), dim3(TR_PLANES_WAVE), 0, (hipStream_t)stream, pl_view(bvh), d_org, d_nrm, out8,
+    hipLaunchKernelGGL(k_planes<MODE>, dim3((unsigned)n), dim3(TR_PLANES_WAVE), 0, (hipStream_t)stream, tr_view_of(bvh), d_org, d_nrm, out8,
                        out32, d_count, d_offsets, total, d_face, reinterpret_cast<int32_t*>(d_segments), cut, frontier_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;
@@ -223,7 +216,7 @@ int tr_planes_any(const tr_bvh* bvh, const float* d_origins, const float* d_norm
     if (int rc = pl_check(bvh, d_origins, d_normals, n, d_any, cut, frontier_entries)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return pl_launch<TR_PLANES_ANY>(bvh, d_origins, d_normals, n, d_any, nullptr, nullptr, nullptr, 0, nullptr, nullptr, cut, frontier_entries,
                                     stream);
 }
@@ -233,7 +226,7 @@ int tr_planes_count(const tr_bvh* bvh, const float* d_origins, const float* d_no
     if (int rc = pl_check(bvh, d_origins, d_normals, n, d_count, cut, frontier_entries)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return pl_launch<TR_PLANES_COUNT>(bvh, d_origins, d_normals, n, nullptr, d_count, nullptr, nullptr, 0, nullptr, nullptr, cut,
                                       frontier_entries, stream);
 }
@@ -249,7 +242,7 @@ int tr_planes_fill(const tr_bvh* bvh, const float* d_origins, const float* d_nor
     if (d_segments && row_blocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many rows for one launch");
     if (n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     if (int rc = pl_launch<TR_PLANES_FILL>(bvh, d_origins, d_normals, n, nullptr, nullptr, d_count, d_offsets, total, d_face, d_segments, cut,
                                            frontier_entries, stream))
         return rc;
@@ -257,7 +250,7 @@ int tr_planes_fill(const tr_bvh* bvh, const float* d_origins, const float* d_nor
                        reinterpret_cast<int32_t*>(d_segments));
     TR_HIP_TRY(hipGetLastError());
     if (d_segments) {
-        hipLaunchKernelGGL(k_planes_segments, dim3((unsigned)row_blocks), dim3(PL_ROWS_BS), 0, (hipStream_t)stream, pl_view(bvh), d_origins,
+        hipLaunchKernelGGL(k_planes_segments, dim3((unsigned)row_blocks), dim3(PL_ROWS_BS), 0, (hipStream_t)stream, tr_view_of(bvh), d_origins,
                            d_normals, n, d_count, d_offsets, total, d_segments);
         TR_HIP_TRY(hipGetLastError());
     }
@@ -272,7 +265,7 @@ int tr_planes_order(int device, int64_t n, const int32_t* d_count, const int64_t
     if (n > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many segments for one launch");
     if (n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, device));
     hipLaunchKernelGGL(k_planes_rows, dim3((unsigned)n), dim3(PL_ROWS_BS), 0, (hipStream_t)stream, d_count, d_offsets, total, d_key,
                        (int32_t*)nullptr);
     TR_HIP_TRY(hipGetLastError());

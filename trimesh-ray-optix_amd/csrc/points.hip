@@ -186,16 +186,14 @@ int tr_contains_points(const tr_bvh* bvh, const float* d_points, int64_t n, cons
     const int64_t nblocks = (n + PT_BS - 1) / PT_BS;
     if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many points for one launch");
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     hipStream_t s = (hipStream_t)stream;
     const void* zeros = nullptr;
     TR_TRY(pt_zeros(bvh->device, &zeros));
     TR_HIP_TRY(hipMemcpyAsync(d_summary2, zeros, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (n > 0) {
         const tr_options opt = tr_opts();   // one snapshot per call
-        tr_bvh_view view;
-        view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-        view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
+        const tr_bvh_view view = tr_view_of(bvh);
         unsigned long long* sum = reinterpret_cast<unsigned long long*>(d_summary2);
         const dim3 grid((unsigned)nblocks), block(PT_BS);
         switch (pt_addressing(bvh, opt)) {

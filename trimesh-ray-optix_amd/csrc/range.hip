@@ -8,7 +8,7 @@
 //  * Rays arrive as tr_rays and are read as every other kernel reads them: RayFetch / fetch_ray of kernels_common.inc
 //    (dense, broadcast and general strides).
 //  * The far-child stack of a lane is a column of LDS: TR_RANGE_STACK = 32 entries of {node, entry distance}, 32 KB per
-//    workgroup.  A lane whose stack overflowed walks the tree again without one (tr_range_rewalk) after the wave's loop.
+//    workgroup.  A lane whose stack overflowed walks the tree again without one (tr_rewalk on a tr_range_probe) after the wave's loop.
 //  * One instantiation per query, 64-bit address arithmetic.
 #include <string>
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(RG_BS) void k_range_query(tr_bvh_view b, RayFetch r
             if (st.node >= 0) tr_range_visit<Q>(b, r, lo, hi, st, best, stack, cap2);
             TR_CONVERGE();
         }
-        if (tr_range_lost(st.sp)) tr_range_rewalk<Q>(b, r, lo, hi, best);
+        if (tr_range_lost(st.sp)) tr_rewalk(b, tr_range_probe<Q>{b, r, lo, hi, best});
     } else if (valid) {
         tr_counters* nc = nullptr;
         const tr_tri w = tr_load_tri<false, false>(b, 0, nc);      // no hierarchy below two triangles
@@ -75,51 +75,12 @@ __global__ __launch_bounds__(RG_BS) void k_range_query(tr_bvh_view b, RayFetch r
 
 namespace {
 
-// tr_rays -> RayFetch: the checks and the stride classes of the other entries (launch_policy.inc, make_fetch)
-int range_fetch(const tr_rays* rays, RayFetch* rf) {
-    if (!rays) return tr_fail(TR_ERR_INVALID_ARG, "rays == NULL");
-    if (rays->nray < 0) return tr_fail(TR_ERR_INVALID_ARG, "nray < 0");
-    if (rays->shape[3] != 3) return tr_fail(TR_ERR_INVALID_ARG, "last ray dimension must be 3");
-    int64_t prod = 1;
-    for (int k = 0; k < 3; k++) {
-        const int64_t s = rays->shape[k];
-        if (s == INT64_MAX) continue;
-        if (s < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative ray dimension");
-        prod *= s;
-    }
-    if (prod != rays->nray) return tr_fail(TR_ERR_INVALID_ARG, "nray != product of leading dims");
-    if (rays->nray > 0 && (!rays->d_origins || !rays->d_directions)) return tr_fail(TR_ERR_INVALID_ARG, "null ray pointer");
-    rf->o = rays->d_origins; rf->d = rays->d_directions; rf->n = rays->nray;
-    rf->s0 = rays->shape[0]; rf->s1 = rays->shape[1]; rf->s2 = rays->shape[2];
-    auto classify = [&](const int64_t* st) {
-        bool bcast = true, dense = st[3] == 1;
-        int64_t expect = 3;
-        for (int k = 2; k >= 0; k--) {
-            const int64_t s = rays->shape[k];
-            if (s == INT64_MAX || s == 1) continue;
-            if (st[k] != 0) bcast = false;
-            if (st[k] != expect) dense = false;
-            expect *= s;
-        }
-        return dense ? 0 : (bcast ? 1 : 2);
-    };
-    for (int k = 0; k < 4; k++) { rf->os[k] = rays->ostride[k]; rf->ds[k] = rays->dstride[k]; }
-    rf->omode = classify(rays->ostride);
-    rf->dmode = classify(rays->dstride);
-    rf->aframe = nullptr;
-    if (rf->s0 == INT64_MAX) rf->s0 = 1;
-    if (rf->s1 == INT64_MAX) rf->s1 = 1;
-    if (rf->s2 == INT64_MAX) rf->s2 = 1;
-    if (rf->s0 == 0 || rf->s1 == 0 || rf->s2 == 0) { rf->s0 = rf->s1 = rf->s2 = 1; }
-    return TR_OK;
-}
-
 template <int Q>
 int range_launch(const tr_bvh* bvh, const tr_rays* rays, const float* d_tmin, const float* d_tmax, const RangeOut& out,
                  const void* required, int stack_entries, void* stream) {
     if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
     RayFetch rf;
-    TR_TRY(range_fetch(rays, &rf));
+    TR_TRY(make_fetch(rays, &rf));
     if (stack_entries < 0 || stack_entries > TR_RANGE_STACK)
         return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_RANGE_STACK));
     if (rf.n > 0 && !required) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
@@ -127,11 +88,8 @@ int range_launch(const tr_bvh* bvh, const tr_rays* rays, const float* d_tmin, co
     if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many rays for one launch");
     if (rf.n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    hipLaunchKernelGGL((k_range_query<Q>), dim3((unsigned)nblocks), dim3(RG_BS), 0, (hipStream_t)stream, view, rf, d_tmin, d_tmax,
+    TR_TRY(tr_enter_device(&guard, bvh->device));
+    hipLaunchKernelGGL((k_range_query<Q>), dim3((unsigned)nblocks), dim3(RG_BS), 0, (hipStream_t)stream, tr_view_of(bvh), rf, d_tmin, d_tmax,
                        out, stack_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;

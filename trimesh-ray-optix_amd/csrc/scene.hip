@@ -83,7 +83,7 @@ __global__ __launch_bounds__(SC_BS) void k_scene_query(const tr_scene_member* __
                 if (st.node >= 0) tr_range_visit<Q>(b, r, lo, hi, st, best, stack, cap2);
                 TR_CONVERGE();
             }
-            if (tr_range_lost(st.sp)) tr_range_rewalk<Q>(b, r, lo, hi, best);
+            if (tr_range_lost(st.sp)) tr_rewalk(b, tr_range_probe<Q>{b, r, lo, hi, best});
         } else if (live) {
             tr_scene_single(b, r, lo, hi, best);      // no hierarchy below two triangles
         }
@@ -98,46 +98,6 @@ __global__ __launch_bounds__(SC_BS) void k_scene_query(const tr_scene_member* __
 
 namespace {
 
-// tr_rays -> RayFetch: the checks and the stride classes of the other entries.  A COPY of range_fetch (range.hip), kept in
-// step by hand because no existing file is touched here: owed to kernels_common.inc as one function
-int scene_fetch(const tr_rays* rays, RayFetch* rf) {
-    if (!rays) return tr_fail(TR_ERR_INVALID_ARG, "rays == NULL");
-    if (rays->nray < 0) return tr_fail(TR_ERR_INVALID_ARG, "nray < 0");
-    if (rays->shape[3] != 3) return tr_fail(TR_ERR_INVALID_ARG, "last ray dimension must be 3");
-    int64_t prod = 1;
-    for (int k = 0; k < 3; k++) {
-        const int64_t s = rays->shape[k];
-        if (s == INT64_MAX) continue;
-        if (s < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative ray dimension");
-        prod *= s;
-    }
-    if (prod != rays->nray) return tr_fail(TR_ERR_INVALID_ARG, "nray != product of leading dims");
-    if (rays->nray > 0 && (!rays->d_origins || !rays->d_directions)) return tr_fail(TR_ERR_INVALID_ARG, "null ray pointer");
-    rf->o = rays->d_origins; rf->d = rays->d_directions; rf->n = rays->nray;
-    rf->s0 = rays->shape[0]; rf->s1 = rays->shape[1]; rf->s2 = rays->shape[2];
-    auto classify = [&](const int64_t* st) {
-        bool bcast = true, dense = st[3] == 1;
-        int64_t expect = 3;
-        for (int k = 2; k >= 0; k--) {
-            const int64_t s = rays->shape[k];
-            if (s == INT64_MAX || s == 1) continue;
-            if (st[k] != 0) bcast = false;
-            if (st[k] != expect) dense = false;
-            expect *= s;
-        }
-        return dense ? 0 : (bcast ? 1 : 2);
-    };
-    for (int k = 0; k < 4; k++) { rf->os[k] = rays->ostride[k]; rf->ds[k] = rays->dstride[k]; }
-    rf->omode = classify(rays->ostride);
-    rf->dmode = classify(rays->dstride);
-    rf->aframe = nullptr;
-    if (rf->s0 == INT64_MAX) rf->s0 = 1;
-    if (rf->s1 == INT64_MAX) rf->s1 = 1;
-    if (rf->s2 == INT64_MAX) rf->s2 = 1;
-    if (rf->s0 == 0 || rf->s1 == 0 || rf->s2 == 0) { rf->s0 = rf->s1 = rf->s2 = 1; }
-    return TR_OK;
-}
-
 tr_scene_member member_of(const tr_bvh* b) {
     tr_scene_member m;
     m.nodes = b->nodes; m.links = b->links; m.tris = b->tris; m.num_tris = b->num_tris;
@@ -149,7 +109,7 @@ int scene_launch(const tr_scene* scene, const tr_rays* rays, const float* d_tmin
                  const void* required, int stack_entries, void* stream) {
     if (!scene) return tr_fail(TR_ERR_INVALID_ARG, "scene == NULL");
     RayFetch rf;
-    TR_TRY(scene_fetch(rays, &rf));
+    TR_TRY(make_fetch(rays, &rf));
     if (stack_entries < 0 || stack_entries > TR_RANGE_STACK)
         return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_RANGE_STACK));
     if (rf.n > 0 && !required) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
@@ -158,7 +118,7 @@ int scene_launch(const tr_scene* scene, const tr_rays* rays, const float* d_tmin
     if (scene_stale(scene)) return tr_fail(TR_ERR_INVALID_ARG, "scene is stale: commit it again");
     if (rf.n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, scene->device));
     hipLaunchKernelGGL((k_scene_query<Q>), dim3((unsigned)nblocks), dim3(SC_BS), 0, (hipStream_t)stream, scene->d_members,
                        scene->d_insts, (int32_t)scene->ninst, rf, d_tmin, d_tmax, out, stack_entries);
     TR_HIP_TRY(hipGetLastError());
@@ -226,7 +186,7 @@ int tr_scene_commit(tr_scene* scene, const tr_bvh* const* members, int64_t nmesh
         memcpy(recs + k, &rec, sizeof(rec));
     }
     tr_device_guard guard;
-    if (bytes > 0 && guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    if (bytes > 0) TR_TRY(tr_enter_device(&guard, scene->device));
     if (bytes > scene->table_bytes) {
         // the new table first: if it cannot be had, the scene keeps its old one
         void* fresh = nullptr;

@@ -32,7 +32,7 @@ constexpr int SX_BS = 128;      // one ray per lane, two waves per workgroup
 }  // namespace
 
 // COUNT: out32[i] = the number of crossings over all instances.  FILL: the crossings of ray i, in walk order, at rows
-// offsets[i] .. of inst, face and t (and their arena slots at the same rows of slot, where given), at most tr_cross_limit.
+// offsets[i] .. of inst, face and t (and their arena slots at the same rows of slot, where given), at most tr_rows_limit.
 template <int MODE>
 __global__ __launch_bounds__(SX_BS) void k_scene_cross(const tr_scene_member* __restrict__ members,
                                                        const tr_scene_inst* __restrict__ insts, int32_t ninst, RayFetch rf,
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(SX_BS) void k_scene_cross(const tr_scene_member* __
     int32_t* irow = nullptr;
     if (MODE == TR_CROSS_FILL && in_range) {
         const int64_t off = offsets[i];
-        acc.limit = tr_cross_limit(count[i], off, total);
+        acc.limit = tr_rows_limit(count[i], off, total);
         if (acc.limit > 0) { acc.face = face + off; acc.t = t + off; acc.slot = slot ? slot + off : nullptr; irow = inst + off; }
     }
     const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_CROSS_STACK);
@@ -83,9 +83,9 @@ __global__ __launch_bounds__(SX_BS) void k_scene_cross(const tr_scene_member* __
                 if (st.node >= 0) tr_cross_visit<MODE>(b, r, lo, hi, st, acc, stack, cap2);
                 TR_CONVERGE();
             }
-            if (tr_cross_lost(st.sp) && !tr_cross_full<MODE>(acc)) {      // cold: this instance's part is dropped, not added to
+            if (tr_walk_lost(st.sp) && !tr_cross_full<MODE>(acc)) {      // cold: this instance's part is dropped, not added to
                 acc.count = c0;
-                tr_cross_rewalk<MODE>(b, r, lo, hi, acc);
+                tr_rewalk(b, tr_cross_probe<MODE>{b, r, lo, hi, acc});
             }
         } else if (live) {
             tr_scene_cross_single<MODE>(b, r, lo, hi, acc);      // no hierarchy below two triangles
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(SX_BS) void k_scene_cross_rows(const tr_scene_membe
     const int64_t i = (int64_t)blockIdx.x * SX_BS + threadIdx.x;
     if (i >= rf.n) return;
     const int64_t off = offsets[i];
-    const int32_t m = tr_cross_limit(count[i], off, total);
+    const int32_t m = tr_rows_limit(count[i], off, total);
     if (m <= 0) return;
     float o[3], d[3];
     fetch_ray(rf, i, o, d);
@@ -118,51 +118,11 @@ __global__ __launch_bounds__(SX_BS) void k_scene_cross_rows(const tr_scene_membe
 
 namespace {
 
-// tr_rays -> RayFetch: the checks and the stride classes of the other entries.  One more COPY of range_fetch (range.hip),
-// kept in step by hand because no existing file is touched here: owed to kernels_common.inc as one function
-int scene_cross_fetch(const tr_rays* rays, RayFetch* rf) {
-    if (!rays) return tr_fail(TR_ERR_INVALID_ARG, "rays == NULL");
-    if (rays->nray < 0) return tr_fail(TR_ERR_INVALID_ARG, "nray < 0");
-    if (rays->shape[3] != 3) return tr_fail(TR_ERR_INVALID_ARG, "last ray dimension must be 3");
-    int64_t prod = 1;
-    for (int k = 0; k < 3; k++) {
-        const int64_t s = rays->shape[k];
-        if (s == INT64_MAX) continue;
-        if (s < 0) return tr_fail(TR_ERR_INVALID_ARG, "negative ray dimension");
-        prod *= s;
-    }
-    if (prod != rays->nray) return tr_fail(TR_ERR_INVALID_ARG, "nray != product of leading dims");
-    if (rays->nray > 0 && (!rays->d_origins || !rays->d_directions)) return tr_fail(TR_ERR_INVALID_ARG, "null ray pointer");
-    rf->o = rays->d_origins; rf->d = rays->d_directions; rf->n = rays->nray;
-    rf->s0 = rays->shape[0]; rf->s1 = rays->shape[1]; rf->s2 = rays->shape[2];
-    auto classify = [&](const int64_t* st) {
-        bool bcast = true, dense = st[3] == 1;
-        int64_t expect = 3;
-        for (int k = 2; k >= 0; k--) {
-            const int64_t s = rays->shape[k];
-            if (s == INT64_MAX || s == 1) continue;
-            if (st[k] != 0) bcast = false;
-            if (st[k] != expect) dense = false;
-            expect *= s;
-        }
-        return dense ? 0 : (bcast ? 1 : 2);
-    };
-    for (int k = 0; k < 4; k++) { rf->os[k] = rays->ostride[k]; rf->ds[k] = rays->dstride[k]; }
-    rf->omode = classify(rays->ostride);
-    rf->dmode = classify(rays->dstride);
-    rf->aframe = nullptr;
-    if (rf->s0 == INT64_MAX) rf->s0 = 1;
-    if (rf->s1 == INT64_MAX) rf->s1 = 1;
-    if (rf->s2 == INT64_MAX) rf->s2 = 1;
-    if (rf->s0 == 0 || rf->s1 == 0 || rf->s2 == 0) { rf->s0 = rf->s1 = rf->s2 = 1; }
-    return TR_OK;
-}
-
 // the checks every entry shares (those of cross_check and scene_launch, without the stale check: the caller makes it after
 // its own argument checks); the RayFetch and nblocks come back
 int scene_cross_check(const tr_scene* scene, const tr_rays* rays, const void* required, int stack_entries, RayFetch& rf, int64_t& nblocks) {
     if (!scene) return tr_fail(TR_ERR_INVALID_ARG, "scene == NULL");
-    TR_TRY(scene_cross_fetch(rays, &rf));
+    TR_TRY(make_fetch(rays, &rf));
     if (stack_entries < 0 || stack_entries > TR_CROSS_STACK)
         return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_CROSS_STACK));
     if (rf.n > 0 && !required) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
@@ -187,7 +147,7 @@ int tr_scene_cross_count(const tr_scene* scene, const tr_rays* rays, const float
     if (scene_stale(scene)) return tr_fail(TR_ERR_INVALID_ARG, "scene is stale: commit it again");
     if (rf.n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, scene->device));
     hipLaunchKernelGGL((k_scene_cross<TR_CROSS_COUNT>), dim3((unsigned)nblocks), dim3(SX_BS), 0, (hipStream_t)stream, scene->d_members,
                        scene->d_insts, (int32_t)scene->ninst, rf, d_tmin, d_tmax, d_count, nullptr, nullptr, (int64_t)0, nullptr, nullptr,
                        nullptr, nullptr, stack_entries);
@@ -209,7 +169,7 @@ int tr_scene_cross_fill(const tr_scene* scene, const tr_rays* rays, const float*
     if (scene_stale(scene)) return tr_fail(TR_ERR_INVALID_ARG, "scene is stale: commit it again");
     if (rf.n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, scene->device));
     if (!evaluate) d_slot = nullptr;
     hipLaunchKernelGGL((k_scene_cross<TR_CROSS_FILL>), dim3((unsigned)nblocks), dim3(SX_BS), 0, (hipStream_t)stream, scene->d_members,
                        scene->d_insts, (int32_t)scene->ninst, rf, d_tmin, d_tmax, nullptr, d_count, d_offsets, total, d_instance, d_face,

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(SN_BS) void k_scene_closest_point(const tr_scene_me
                     if (st.node >= 0) tr_scene_near_visit(b, M, px, py, pz, st, best, stack, cap2);
                     TR_CONVERGE();
                 }
-                if (tr_near_lost(st.sp)) tr_scene_near_rewalk(b, M, px, py, pz, best);      // cold
+                if (tr_near_lost(st.sp)) tr_rewalk(b, tr_scene_near_probe{b, M, px, py, pz, best});      // cold
             } else if (valid) {
                 tr_scene_near_leaf(b, M, 0, px, py, pz, best);      // no hierarchy below two triangles
             }
@@ -118,7 +118,7 @@ int tr_scene_closest_point(const tr_scene* scene, const float* d_points, int64_t
     if (scene_stale(scene)) return tr_fail(TR_ERR_INVALID_ARG, "scene is stale: commit it again");
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, scene->device));
     hipLaunchKernelGGL(k_scene_closest_point, dim3((unsigned)nblocks), dim3(SN_BS), 0, (hipStream_t)stream, scene->d_members, scene->d_insts,
                        (int32_t)scene->ninst, d_points, n, d_max_distance, max_distance, d_closest, d_distance, d_instance, d_tri,
                        stack_entries);

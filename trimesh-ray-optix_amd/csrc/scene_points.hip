@@ -41,7 +41,7 @@ __device__ __forceinline__ float sp_uniform(float x) {
 }  // namespace
 
 // ANY: out8[i] = the point is inside some instance.  COUNT: out32[i] = the number of instances it is inside.  FILL: those
-// instances, ascending, at rows offsets[i] .. of inst, at most tr_cross_limit(count[i], offsets[i], total) of them.
+// instances, ascending, at rows offsets[i] .. of inst, at most tr_rows_limit(count[i], offsets[i], total) of them.
 template <int MODE>
 __global__ __launch_bounds__(SP_BS) void k_scene_points(const tr_scene_member* __restrict__ members,
                                                         const tr_scene_inst* __restrict__ insts, int32_t ninst,
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(SP_BS) void k_scene_points(const tr_scene_member* _
     acc.count = 0; acc.limit = 0; acc.inst = nullptr;
     if (MODE == TR_SCENE_POINTS_FILL && in_range) {
         const int64_t off = offsets[i];
-        acc.limit = tr_cross_limit(count[i], off, total);
+        acc.limit = tr_rows_limit(count[i], off, total);
         if (acc.limit > 0) acc.inst = inst + off;
     }
     float lo, hi;
@@ -92,9 +92,9 @@ __global__ __launch_bounds__(SP_BS) void k_scene_points(const tr_scene_member* _
                     if (st.node >= 0) tr_cross_visit<TR_CROSS_COUNT>(b, r, lo, hi, st, ca, stack, cap2);
                     TR_CONVERGE();
                 }
-                if (tr_cross_lost(st.sp)) {      // cold: this pass's count is dropped, not added to
+                if (tr_walk_lost(st.sp)) {      // cold: this pass's count is dropped, not added to
                     ca.count = 0;
-                    tr_cross_rewalk<TR_CROSS_COUNT>(b, r, lo, hi, ca);
+                    tr_rewalk(b, tr_cross_probe<TR_CROSS_COUNT>{b, r, lo, hi, ca});
                 }
             } else if (live) {
                 tr_scene_cross_single<TR_CROSS_COUNT>(b, r, lo, hi, ca);      // no hierarchy below two triangles
@@ -137,7 +137,7 @@ int scene_points_launch(const tr_scene* scene, const float* d_points, int64_t n,
                         const int32_t* d_count, const int64_t* d_offsets, int64_t total, int32_t* d_instance, int stack_entries,
                         int64_t nblocks, void* stream) {
     tr_device_guard guard;
-    if (guard.enter(scene->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, scene->device));
     hipLaunchKernelGGL((k_scene_points<MODE>), dim3((unsigned)nblocks), dim3(SP_BS), 0, (hipStream_t)stream, scene->d_members,
                        scene->d_insts, (int32_t)scene->ninst, d_points, n, d_dir3, d_any, d_out, d_count, d_offsets, total, d_instance,
                        stack_entries);

@@ -1,5 +1,5 @@
 // tr_boxes.h -- box queries (include/triro_boxes.h): the faces of a mesh that meet an axis-aligned box.  Host + device, as
-// tr_within.h, whose row limit and ordering it uses UNCHANGED: k_boxes<> and k_boxes_rows (boxes.hip) instantiate the walk
+// tr_within.h, whose ordering it uses UNCHANGED, on the set walk and the row limit of tr_walk.h: k_boxes<> and k_boxes_rows (boxes.hip) instantiate the walk
 // per lane, tests/host_sim/boxes_sim.cpp compiles the very same functions with g++.  Not a CPU fallback: nothing in the C
 // ABI reaches the host instantiation.
 //
@@ -46,14 +46,14 @@
 // a superset), so max(a_k, b_k, c_k) <= node_hi_k < lo_k or min(a_k, b_k, c_k) >= node_lo_k > hi_k: step 1 of the predicate
 // separates it, with the same exact comparisons.  A skipped subtree holds no face that meets the box.  No rounding argument.
 //
-// THE WALK is the set walk of tr_within.h (tr_within_visit) with this culling and this leaf: one 64-byte node per visit, both
-// child boxes tested, leaf children that survive evaluated and recorded (FILL), counted (COUNT) or ending the walk (ANY); of
-// the internal children that survive, child 0 is visited next and child 1 pushed (no order is better than another: the whole
-// set is wanted).  Stack entries are NODE IDS ONLY, TR_BOXES_STACK = 32 per lane, a column of LDS; a push that does not fit
-// sets the sticky lost bit, and a lane that ends with it set DISCARDS its partial count / write cursor and repeats the walk
-// without a stack through the parent links (tr_boxes_rewalk).  Each walk visits a node at most once: nothing is counted twice.
-// Below two triangles there is no hierarchy: the one triangle is tested directly.
-// FILL writes, in walk order and never beyond `limit` = tr_within_limit(count, offset, total) rows, one KEY per face:
+// THE WALK is THE SET WALK of tr_walk.h with this culling and this leaf: of the internal children that survive, child 0 is
+// visited next and child 1 pushed (no order is better than another: the whole set is wanted); TR_BOXES_STACK = 32 node ids
+// per lane.  The stack, the row limit and the ordering are the shared ones; tr_boxes_visit, tr_boxes_rewalk, tr_boxes_query and
+// the body of k_boxes are tr_set_visit, tr_rewalk, tr_set_query and tr_set_kernel WRITTEN OUT: built on those (as tr_tris.h
+// is, through tr_set_probe below) the kernels kept their registers and LDS but the FILL instantiation was laid out anew,
+// and faces_in_boxes on hashed boxes measured 0.5 % slower than the commit before, outside the spread of that commit
+// against itself -- so this kernel keeps its text, and compiles to the same instructions as before.
+// FILL writes, in walk order and never beyond `limit` = tr_rows_limit(count, offset, total) rows, one KEY per face:
 // tr_boxes_key = (2 * face + inside) with the top bit flipped, an int32 whose signed order is the order of the faces -- the
 // `inside` flag rides through the ordering without scratch.  tr_boxes_rows then orders the segment (tr_within_sort) and
 // unpacks face and inside.
@@ -62,7 +62,7 @@
 
 #define TR_BOXES_STACK 32      // node ids per lane: 32 x 4 B x 128 lanes = 16 KB of LDS per workgroup
 
-enum tr_boxes_mode { TR_BOXES_ANY = 0, TR_BOXES_COUNT = 1, TR_BOXES_FILL = 2 };
+enum tr_boxes_mode { TR_BOXES_ANY = TR_SET_ANY, TR_BOXES_COUNT = TR_SET_COUNT, TR_BOXES_FILL = TR_SET_FILL };
 
 struct tr_box { float lox, loy, loz, hix, hiy, hiz; };
 
@@ -135,12 +135,6 @@ TR_HD int32_t tr_boxes_key(int32_t face, bool inside) { return (int32_t)((2u * (
 TR_HD int32_t tr_boxes_key_face(int32_t key) { return (int32_t)(((uint32_t)key ^ 0x80000000u) >> 1); }
 TR_HD bool tr_boxes_key_inside(int32_t key) { return ((uint32_t)key & 1u) != 0; }
 
-// the walk has what it came for: ANY a face, FILL all its rows
-template <int MODE>
-TR_HD bool tr_boxes_full(const tr_boxes_acc& acc) {
-    return MODE == TR_BOXES_ANY ? acc.count > 0 : (MODE == TR_BOXES_FILL ? acc.count >= acc.limit : false);
-}
-
 // one triangle against the box
 template <int MODE>
 TR_HD void tr_boxes_leaf(const tr_bvh_view& b, int32_t slot, const tr_box& q, tr_boxes_acc& acc) {
@@ -165,36 +159,36 @@ TR_HD tr_boxes_node tr_boxes_load(const tr_bvh_view& b, int32_t node, const tr_b
     return r;
 }
 
-// visit st.node (>= 0): see THE WALK (state and stack are tr_within.h's: node ids in a column of a tr_ring)
+// visit st.node (>= 0): see THE WALK
 template <int MODE>
-TR_HD void tr_boxes_visit(const tr_bvh_view& b, const tr_box& q, tr_within_state& st, tr_boxes_acc& acc, const tr_ring stack, uint32_t cap2) {
+TR_HD void tr_boxes_visit(const tr_bvh_view& b, const tr_box& q, tr_walk_state& st, tr_boxes_acc& acc, const tr_ring stack, uint32_t cap2) {
     const tr_boxes_node n = tr_boxes_load(b, st.node, q);
 #pragma unroll 1
     for (int k = 0; k < 2; k++) {
         const int32_t c = k ? n.c1 : n.c0;
         const bool apart = k ? n.apart1 : n.apart0;
-        if (c < 0 && !apart && !tr_boxes_full<MODE>(acc)) tr_boxes_leaf<MODE>(b, ~c, q, acc);
+        if (c < 0 && !apart && !tr_set_full<MODE>(acc)) tr_boxes_leaf<MODE>(b, ~c, q, acc);
     }
-    if (tr_boxes_full<MODE>(acc)) { st.node = -1; return; }
+    if (tr_set_full<MODE>(acc)) { st.node = -1; return; }
     const bool go0 = n.c0 >= 0 && !n.apart0, go1 = n.c1 >= 0 && !n.apart1;
     if (go0) {
-        if (go1) tr_within_push(stack, cap2, st.sp, n.c1);
+        if (go1) tr_walk_push(stack, cap2, st.sp, n.c1);
         st.node = n.c0;
     } else if (go1) {
         st.node = n.c1;
     } else {
-        st.node = tr_within_pop(stack, st.sp);
+        st.node = tr_walk_pop(stack, st.sp);
     }
 }
 
-// the whole tree again without a stack (after a lost push; the caller has reset acc.count): children in fixed order, up
-// through the parent links.  phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
+// the whole tree again without a stack (after a lost push; the caller has reset acc.count): the loop of tr_rewalk (tr_walk.h)
+// written out, as the visit above and tr_boxes_query below are tr_set_visit's and tr_set_query's -- see THE WALK for why
 template <int MODE>
 TR_HD void tr_boxes_rewalk(const tr_bvh_view& b, const tr_box& q, tr_boxes_acc& acc) {
     int32_t node = 0;
     int phase = 0;
     for (;;) {
-        if (tr_boxes_full<MODE>(acc)) break;
+        if (tr_set_full<MODE>(acc)) break;
         if (phase == 2) {
             const int32_t parent = b.links[node].parent;
             if (parent < 0) break;
@@ -216,6 +210,48 @@ TR_HD void tr_boxes_rewalk(const tr_bvh_view& b, const tr_box& q, tr_boxes_acc& 
     }
 }
 
+// THE SET WALK ON A BOX (tr_walk.h), for a query that culls by an axis-aligned box `box` and evaluates a leaf with
+// leaf(slot, acc): tris with the box of the query triangle.  Visit st.node (>= 0): of the internal children whose boxes the
+// query's box is not apart from, child 0 is visited next and child 1 pushed.
+template <int MODE, class Leaf>
+TR_HD void tr_set_visit(const tr_bvh_view& b, const tr_box& box, const Leaf& leaf, tr_walk_state& st, tr_boxes_acc& acc,
+                        const tr_ring stack, uint32_t cap2) {
+    const tr_boxes_node n = tr_boxes_load(b, st.node, box);
+#pragma unroll 1
+    for (int k = 0; k < 2; k++) {
+        const int32_t c = k ? n.c1 : n.c0;
+        const bool apart = k ? n.apart1 : n.apart0;
+        if (c < 0 && !apart && !tr_set_full<MODE>(acc)) leaf(~c, acc);
+    }
+    if (tr_set_full<MODE>(acc)) { st.node = -1; return; }
+    const bool go0 = n.c0 >= 0 && !n.apart0, go1 = n.c1 >= 0 && !n.apart1;
+    if (go0) {
+        if (go1) tr_walk_push(stack, cap2, st.sp, n.c1);
+        st.node = n.c0;
+    } else if (go1) {
+        st.node = n.c1;
+    } else {
+        st.node = tr_walk_pop(stack, st.sp);
+    }
+}
+// ... and the query as tr_walk.h sees it (tr_rewalk, tr_set_query, tr_set_kernel)
+template <int MODE, class Leaf>
+struct tr_set_probe {
+    const tr_bvh_view& b;
+    const tr_box& box;
+    const Leaf test;
+    tr_boxes_acc& acc;
+    TR_HDM bool done() const { return tr_set_full<MODE>(acc); }
+    TR_HDM void leaf(int32_t slot) const { test(slot, acc); }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
+        const tr_boxes_node n = tr_boxes_load(b, node, box);
+        c = phase ? n.c1 : n.c0;
+        return !(phase ? n.apart1 : n.apart0);
+    }
+    TR_HDM void visit(tr_walk_state& st, const tr_ring stack, uint32_t cap2) const {
+        tr_set_visit<MODE>(b, box, test, st, acc, stack, cap2);
+    }
+};
 // order the m rows (keys) of a box, then unpack them: face in place, inside where asked for
 TR_HD void tr_boxes_rows(int32_t* face, uint8_t* inside, int32_t m) {
     tr_within_sort(face, nullptr, m);
@@ -234,17 +270,17 @@ TR_HD int32_t tr_boxes_query(const tr_bvh_view& b, const tr_box& q, const tr_rin
     const bool valid = tr_box_valid(q) && b.num_tris > 0;
     acc.count = 0;
     if (lost) *lost = false;
-    if (valid && b.num_tris >= 2 && !tr_boxes_full<MODE>(acc)) {
+    if (valid && b.num_tris >= 2 && !tr_set_full<MODE>(acc)) {
         const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_BOXES_STACK);
-        tr_within_state st;
+        tr_walk_state st;
         st.node = 0; st.sp = 0;
         while (st.node >= 0) tr_boxes_visit<MODE>(b, q, st, acc, stack, cap2);
-        if (lost) *lost = tr_within_lost(st.sp);
-        if (tr_within_lost(st.sp) && !tr_boxes_full<MODE>(acc)) {
+        if (lost) *lost = tr_walk_lost(st.sp);
+        if (tr_walk_lost(st.sp) && !tr_set_full<MODE>(acc)) {
             acc.count = 0;
             tr_boxes_rewalk<MODE>(b, q, acc);
         }
-    } else if (valid && !tr_boxes_full<MODE>(acc)) {
+    } else if (valid && !tr_set_full<MODE>(acc)) {
         tr_boxes_leaf<MODE>(b, 0, q, acc);      // no hierarchy below two triangles
     }
     return acc.count;

@@ -41,13 +41,12 @@
 // (st.pe0 / st.pe1, one per child) and tr_cross_drain decides it at the END of the visit -- tr_range_drain's sequence: a
 // wave-uniform cold skip, the triangle fetched again for the tie question -- and counts or records the hit where
 // tr_range_drain folds a best.
-// A push that does not fit sets the sticky lost bit of st.sp; a lane that ends with it set DISCARDS its partial count / write
-// cursor and repeats the whole walk without a stack, through the parent links (tr_cross_rewalk, as tr_within_rewalk /
-// tr_range_rewalk): nothing is counted twice.  Each walk visits a node at most once, so the crossings one walk records are
-// distinct.  Below two triangles there is no hierarchy: the one triangle is tested directly (tr_range_tri).
+// The node-id stack, the lost bit and the re-walk of a lane that lost a push (tr_rewalk on a tr_cross_probe; the partial count
+// / write cursor is DISCARDED first, so nothing is counted twice) are THE SET WALK of tr_walk.h.  Below two triangles there
+// is no hierarchy: the one triangle is tested directly (tr_range_tri).
 //
 // FILL writes (face, t, slot) of a ray's crossings in walk order at its rows -- never more than `limit`, the rows the caller's
-// count[i], offsets[i] and total leave the ray (tr_cross_limit: [off, off + count) cut to [0, total); nothing for a
+// count[i], offsets[i] and total leave the ray (tr_rows_limit: [off, off + count) cut to [0, total); nothing for a
 // negative count or an offset outside), whatever the walk finds -- and ends once they are full.
 // ROWS (tr_cross_rows) then orders the m rows of a ray in place -- a heapsort on (t, face) that carries t, face and slot
 // together; no scratch, and every index it forms is below m whatever the rows hold, NaN keys included (a NaN compares false
@@ -74,7 +73,6 @@ struct tr_cross_state {
     int32_t pe0, pe1;   // leaf tests waiting for the float64 part (tri slots, -1 = none): nearer / farther child
 };
 
-TR_HD bool tr_cross_lost(uint32_t sp) { return (sp & 1u) != 0; }
 // the walk has what it came for: FILL all its rows
 template <int MODE>
 TR_HD bool tr_cross_full(const tr_cross_acc& acc) { return MODE == TR_CROSS_FILL ? acc.count >= acc.limit : false; }
@@ -124,22 +122,6 @@ TR_HD void tr_cross_drain(const tr_bvh_view& b, const tr_ray& r, float lo, float
     }
 }
 
-// Stack: entry e of a lane is word e of its column of a tr_ring.  cap2 = 2 * entries the walk may use.
-TR_HD void tr_cross_push(const tr_ring stack, uint32_t cap2, uint32_t& sp, int32_t node) {
-    const uint32_t w = sp & ~1u;
-    if (w < cap2) {
-        tr_ring_put(stack, w >> 1, node);
-        sp += 2u;
-    } else {
-        sp |= 1u;
-    }
-}
-TR_HD int32_t tr_cross_pop(const tr_ring stack, uint32_t& sp) {
-    if (sp < 2u) return -1;
-    sp -= 2u;
-    return tr_ring_get(stack, sp >> 1);
-}
-
 // visit st.node (>= 0): see THE WALK
 template <int MODE>
 TR_HD void tr_cross_visit(const tr_bvh_view& b, const tr_ray& r, float lo, float hi, tr_cross_state& st, tr_cross_acc& acc,
@@ -166,12 +148,12 @@ TR_HD void tr_cross_visit(const tr_bvh_view& b, const tr_ray& r, float lo, float
     }
     const bool go_n = cn >= 0 && tr_range_box(tnn, tfn, lim, cut), go_f = cf >= 0 && tr_range_box(tnf, tff, lim, cut);
     if (go_n) {
-        if (go_f) tr_cross_push(stack, cap2, st.sp, cf);
+        if (go_f) tr_walk_push(stack, cap2, st.sp, cf);
         st.node = cn;
     } else if (go_f) {
         st.node = cf;
     } else {
-        st.node = tr_cross_pop(stack, st.sp);
+        st.node = tr_walk_pop(stack, st.sp);
     }
     // the end of the visit: the float64 half of what the leaf tests parked
     tr_cross_drain<MODE>(b, r, lo, hi, st.pe0, acc);
@@ -179,73 +161,47 @@ TR_HD void tr_cross_visit(const tr_bvh_view& b, const tr_ray& r, float lo, float
     if (tr_cross_full<MODE>(acc)) st.node = -1;
 }
 
-// the whole tree again without a stack (after a lost push; the caller has reset acc.count): children in fixed order, up
-// through the parent links.  phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
+// the whole tree again without a stack (after a lost push; the caller has reset acc.count):
+// tr_rewalk(b, tr_cross_probe<MODE>{b, r, lo, hi, acc}) -- a child is culled as in the walk, a leaf is tested and what it
+// parked decided at once
 template <int MODE>
-TR_HD void tr_cross_rewalk(const tr_bvh_view& b, const tr_ray& r, float lo, float hi, tr_cross_acc& acc) {
-    const float lim = hi * TR_CULL_SLACK, cut = lo * TR_RANGE_LO_CUT;
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (tr_cross_full<MODE>(acc)) break;
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
+struct tr_cross_probe {
+    const tr_bvh_view& b;
+    const tr_ray& r;
+    float lo, hi;
+    tr_cross_acc& acc;
+    TR_HDM bool done() const { return tr_cross_full<MODE>(acc); }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
         const tr_f4* q = reinterpret_cast<const tr_f4*>(b.nodes + node);
         const tr_f4 n0 = q[0], n1 = q[1], n2 = q[2], n3 = q[3];
         float tn0, tf0, tn1, tf1;
         tr_node_slabs(r, n0, n1, n2, tn0, tf0, tn1, tf1);
-        const int32_t c = (int32_t)tr_f2u(phase ? n3.y : n3.x);
-        const float tn = phase ? tn1 : tn0, tf = phase ? tf1 : tf0;
-        phase++;
-        if (!tr_range_box(tn, tf, lim, cut)) continue;
-        if (c < 0) {
-            int32_t pe = -1;
-            tr_cross_leaf<MODE>(b, r, lo, hi, ~c, acc, pe);
-            tr_cross_drain<MODE>(b, r, lo, hi, pe, acc);
-        } else {
-            node = c;
-            phase = 0;
-        }
+        c = (int32_t)tr_f2u(phase ? n3.y : n3.x);
+        return tr_range_box(phase ? tn1 : tn0, phase ? tf1 : tf0, hi * TR_CULL_SLACK, lo * TR_RANGE_LO_CUT);
     }
-}
+    TR_HDM void leaf(int32_t slot) const {
+        int32_t pe = -1;
+        tr_cross_leaf<MODE>(b, r, lo, hi, slot, acc, pe);
+        tr_cross_drain<MODE>(b, r, lo, hi, pe, acc);
+    }
+};
 
-// the rows a ray may write: [off, off + count) cut to [0, total); nothing for a negative count or an offset outside
-TR_HD int32_t tr_cross_limit(int32_t count, int64_t off, int64_t total) {
-    if (count <= 0 || off < 0 || off >= total) return 0;
-    const int64_t room = total - off;
-    return (int64_t)count < room ? count : (int32_t)room;
-}
+// the rows a ray may write: tr_rows_limit under the name the host simulations of cross, scene_cross and scene_points call
+TR_HD int32_t tr_cross_limit(int32_t count, int64_t off, int64_t total) { return tr_rows_limit(count, off, total); }
 
-// m rows into ascending (t, face) order, in place; s (the slots beside them) may be null.  A heapsort: no scratch, and every
-// index it forms is below m whatever the rows hold (the comparisons only choose between indices already bounded by `end`).
-TR_HD void tr_cross_swap(float* t, int32_t* f, int32_t* s, int32_t i, int32_t j) {
-    const float x = t[i]; t[i] = t[j]; t[j] = x;
-    const int32_t a = f[i]; f[i] = f[j]; f[j] = a;
-    if (s) { const int32_t c = s[i]; s[i] = s[j]; s[j] = c; }
-}
-TR_HD bool tr_cross_before(const float* t, const int32_t* f, int32_t i, int32_t j) { return tr_closer(t[i], f[i], t[j], f[j]); }
-TR_HD void tr_cross_sift(float* t, int32_t* f, int32_t* s, int32_t root, int32_t end) {
-    for (;;) {
-        int32_t child = 2 * root + 1;
-        if (child >= end) break;
-        if (child + 1 < end && tr_cross_before(t, f, child, child + 1)) child++;
-        if (!tr_cross_before(t, f, root, child)) break;
-        tr_cross_swap(t, f, s, root, child);
-        root = child;
+// m rows into ascending (t, face) order, in place (tr_rows_sort); s (the slots beside them) may be null
+struct tr_cross_sorted {
+    float* t;
+    int32_t* f;
+    int32_t* s;
+    TR_HDM bool before(int32_t i, int32_t j) const { return tr_closer(t[i], f[i], t[j], f[j]); }
+    TR_HDM void swap(int32_t i, int32_t j) const {
+        const float x = t[i]; t[i] = t[j]; t[j] = x;
+        const int32_t a = f[i]; f[i] = f[j]; f[j] = a;
+        if (s) { const int32_t c = s[i]; s[i] = s[j]; s[j] = c; }
     }
-}
-TR_HD void tr_cross_sort(float* t, int32_t* f, int32_t* s, int32_t m) {
-    for (int32_t i = m / 2 - 1; i >= 0; i--) tr_cross_sift(t, f, s, i, m);
-    for (int32_t end = m - 1; end > 0; end--) {
-        tr_cross_swap(t, f, s, 0, end);
-        tr_cross_sift(t, f, s, 0, end);
-    }
-}
+};
+TR_HD void tr_cross_sort(float* t, int32_t* f, int32_t* s, int32_t m) { tr_rows_sort(tr_cross_sorted{t, f, s}, m); }
 
 // order the m rows of a ray and evaluate the optional outputs of each (slot is required for front / loc3 / uv2): as
 // tr_range_outputs evaluates its winner.  ray (may be null) gets ray_id in every row.
@@ -284,10 +240,10 @@ TR_HD int32_t tr_cross_query(const tr_bvh_view& b, float ox, float oy, float oz,
         tr_cross_state st;
         st.node = 0; st.sp = 0; st.pe0 = -1; st.pe1 = -1;
         while (st.node >= 0) tr_cross_visit<MODE>(b, r, lo, hi, st, acc, stack, cap2);
-        if (lost) *lost = tr_cross_lost(st.sp) ? 1 : 0;
-        if (tr_cross_lost(st.sp) && !tr_cross_full<MODE>(acc)) {
+        if (lost) *lost = tr_walk_lost(st.sp) ? 1 : 0;
+        if (tr_walk_lost(st.sp) && !tr_cross_full<MODE>(acc)) {
             acc.count = 0;
-            tr_cross_rewalk<MODE>(b, r, lo, hi, acc);
+            tr_rewalk(b, tr_cross_probe<MODE>{b, r, lo, hi, acc});
         }
     } else if (valid && !tr_cross_full<MODE>(acc)) {
         tr_counters* nc = nullptr;

@@ -104,6 +104,14 @@ struct tr_bvh {
     bool have_last_launch = false;
 };
 
+// what the kernels are handed of a handle: the one place that knows the fields of tr_bvh_view
+inline tr_bvh_view tr_view_of(const tr_bvh* bvh) {
+    tr_bvh_view view;
+    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
+    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
+    return view;
+}
+
 // bvh->frame -> bvh->frame_dev (a small synchronous copy; build / refit / load have just synchronised anyway)
 int tr_bvh_sync_frame(tr_bvh* bvh);
 
@@ -172,6 +180,30 @@ struct tr_device_guard {
 // ... and the preamble of such an entry point: tr_device_guard g; TR_TRY(tr_enter_device(&g, device));
 inline int tr_enter_device(tr_device_guard* g, int device) {
     return g->enter(device) == TR_OK ? TR_OK : tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+}
+
+// The argument checks of an entry that takes one query per lane, TR_LANE_BS of them per block, on a per-lane stack of at most
+// `capacity` entries (boxes, tris, within, nearest): inputs = every input array was given, noun = what the queries are called
+// in the one message that names them; nblocks comes back.
+constexpr int TR_LANE_BS = 128;
+inline int tr_lane_check(const tr_bvh* bvh, bool inputs, int64_t n, const void* d_required, int stack_entries, int capacity,
+                         const char* noun, int64_t& nblocks) {
+    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
+    if (n < 0) return tr_fail(TR_ERR_INVALID_ARG, "n < 0");
+    if (stack_entries < 0 || stack_entries > capacity)
+        return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(capacity));
+    if (n > 0 && (!inputs || !d_required)) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
+    nblocks = (n + TR_LANE_BS - 1) / TR_LANE_BS;
+    if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, std::string("too many ") + noun + " for one launch");
+    return TR_OK;
+}
+// ... and what their _fill entries check after it: rows = every row array that `total > 0` needs was given, rows_msg = the
+// message that names them
+inline int tr_fill_check(int64_t n, int64_t total, const int64_t* d_offsets, bool rows, const char* rows_msg) {
+    if (total < 0) return tr_fail(TR_ERR_INVALID_ARG, "total < 0");
+    if (n > 0 && !d_offsets) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
+    if (n > 0 && total > 0 && !rows) return tr_fail(TR_ERR_INVALID_ARG, rows_msg);
+    return TR_OK;
 }
 
 // options ---------------------------------------------------------------------------------

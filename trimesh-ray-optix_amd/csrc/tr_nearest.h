@@ -53,13 +53,13 @@
 // child boxes of the node are bounded; leaves among the children are evaluated at once, the nearer first; of the internal children that survive the (updated) best, the nearer is
 // visited next and the farther is pushed on the per-lane stack as {node, bound}.  With no child left the stack is
 // popped.  The stack holds `stack_entries` entries (1 .. TR_NEAR_STACK); a push that does not fit is dropped and sets
-// the sticky `lost` bit of st.sp.  A walk that ends with `lost` set is followed by tr_near_rewalk: the whole tree again
+// the sticky `lost` bit of st.sp.  A walk that ends with `lost` set is followed by tr_rewalk on a tr_near_probe: the whole tree again
 // without a stack, children in fixed order, up through the parent links (tr_link), culling against the best already
 // found -- near-optimal, so this second walk is short.  The winner is a lexicographic minimum over candidates: the
 // second walk yields the same bits.  Cold, correct, not fast.  The builder guarantees a depth of at most 64; nothing
 // here depends on the depth.  Below two triangles there is no hierarchy: the one triangle is evaluated directly.
 #pragma once
-#include "tr_bvh.h"
+#include "tr_walk.h"
 
 #define TR_NEAR_STACK 32      // entries of {node, bound} per lane: 32 x 8 B x 128 lanes = 32 KB of LDS per workgroup; no walk of a hierarchy of up to 32 levels overflows it (tr_near_seed)
 
@@ -241,32 +241,20 @@ TR_HD int32_t tr_near_seed(const tr_bvh_view& b, int32_t node, float px, float p
     return -1;
 }
 
-// the whole tree again without a stack (after a lost push): children in fixed order, up through the parent links.
-// phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
-TR_HD void tr_near_rewalk(const tr_bvh_view& b, float px, float py, float pz, tr_near_best& best) {
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
+// the whole tree again without a stack (after a lost push): tr_rewalk(b, tr_near_probe{b, px, py, pz, best}) -- never done
+// early, a child is culled against the best so far
+struct tr_near_probe {
+    const tr_bvh_view& b;
+    float px, py, pz;
+    tr_near_best& best;
+    TR_HDM bool done() const { return false; }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
         const tr_near_node n = tr_near_load(b, node, px, py, pz);
-        const int32_t c = phase ? n.c1 : n.c0;
-        const double lb = phase ? n.lb1 : n.lb0;
-        phase++;
-        if (lb > best.d2) continue;
-        if (c < 0) {
-            tr_near_leaf(b, ~c, px, py, pz, best);
-        } else {
-            node = c;
-            phase = 0;
-        }
+        c = phase ? n.c1 : n.c0;
+        return !((phase ? n.lb1 : n.lb0) > best.d2);
     }
-}
+    TR_HDM void leaf(int32_t slot) const { tr_near_leaf(b, slot, px, py, pz, best); }
+};
 
 // the three outputs of a point from the best triangle (valid = finite point; best.slot < 0: no triangle).  Any of the
 // pointers may be null.
@@ -302,7 +290,7 @@ TR_HD void tr_near_query(const tr_bvh_view& b, float px, float py, float pz, con
         for (int32_t node = 0; node >= 0;) node = tr_near_seed(b, node, px, py, pz, best);
         st.node = 0; st.sp = 0;
         while (st.node >= 0) tr_near_visit(b, px, py, pz, st, best, stack, cap2);
-        if (tr_near_lost(st.sp)) tr_near_rewalk(b, px, py, pz, best);
+        if (tr_near_lost(st.sp)) tr_rewalk(b, tr_near_probe{b, px, py, pz, best});
     } else if (valid) {
         tr_near_leaf(b, 0, px, py, pz, best);      // no hierarchy below two triangles
     }

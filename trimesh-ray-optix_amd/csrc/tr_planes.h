@@ -1,6 +1,6 @@
 // tr_planes.h -- plane queries (include/triro_planes.h): the faces of a mesh that a plane meets, and the segments in which it
 // cuts them (the section of trimesh.intersections.mesh_plane / mesh_multiplane).  Host + device, as tr_boxes.h, whose row limit
-// (tr_within_limit) and activity rule (tr_near_active) it uses UNCHANGED: k_planes<>, k_planes_rows and k_planes_segments
+// (tr_rows_limit) and activity rule (tr_near_active) it uses UNCHANGED: k_planes<>, k_planes_rows and k_planes_segments
 // (planes.hip) run these functions per lane, tests/host_sim/planes_sim.cpp compiles the very same functions with g++ and drives
 // them for a simulated wave of 64 lanes.  Not a CPU fallback: nothing in the C ABI reaches the host instantiation.
 //
@@ -62,7 +62,9 @@
 // wave-uniform cursor: one wave owns the plane, no atomic is needed, and FILL never writes at or beyond its limit.
 // OVERFLOW.  A push whose position is at or beyond the capacity is not lost: its lane keeps the child as the root of a SUBTREE
 // WALK (tr_planes_sub) and walks that subtree to the end without a stack, children in fixed order, up through the parent links,
-// stopping when it is back at the subtree's root -- tr_boxes_rewalk bounded to a subtree.  A lane can overflow with both children
+// stopping when it is back at the subtree's root -- the tr_rewalk of tr_walk.h bounded to a subtree.  (Not folded into it: this
+// one is RESUMABLE, one candidate per call with its state in the lane between calls, and stops at a root that is not the
+// tree's; the shared loop would need a flag for each.)  A lane can overflow with both children
 // of one round: the second waits in `next`.  The subtree walks run as a wave loop of their own (each lane advances to its next
 // candidate, tr_planes_sub_next; the candidates are then recorded in converged code as above) and have priority: rounds resume
 // when no lane has a subtree left, so a lane never holds more than the two roots of one round.  A node is entered from exactly

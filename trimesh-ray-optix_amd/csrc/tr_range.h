@@ -62,7 +62,7 @@
 // the farther is pushed as {node, tn}.  With no child left the stack is popped; a pop drops an entry whose tn is beyond the
 // current limit without loading its node.  The stack holds `stack_entries` entries (1 .. TR_RANGE_STACK) in LDS: 8 B x 32 x
 // 128 lanes = 32 KB per workgroup.  A push that does not fit is dropped and sets the sticky `lost` bit of st.sp; a lane that
-// ends with it walks the whole tree again without a stack (tr_range_rewalk: children in fixed order, up through the
+// ends with it walks the whole tree again without a stack (tr_rewalk on a tr_range_probe: children in fixed order, up through the
 // parent links, tr_link), culling against what it has.  Same bits: the minimum is lexicographic and any is a
 // disjunction.  An any-ray stops at its first accepted hit.  Below two triangles there is no hierarchy: the one triangle
 // is tested directly.
@@ -71,7 +71,7 @@
 // the node record and the triangle are dead -- as tr_fold_leaf / tr_drain_exact do, and for the reason given there.
 // Until then the candidate culls nothing, which changes no result.
 #pragma once
-#include "tr_bvh.h"
+#include "tr_walk.h"
 
 #define TR_RANGE_STACK 32                    // entries of {node, tn} per lane
 #define TR_RANGE_BAND 9.765625e-4f           // 2^-10: half-width of a bound's band, relative
@@ -243,40 +243,29 @@ TR_HD void tr_range_visit(const tr_bvh_view& b, const tr_ray& r, float lo, float
     if (Q == TR_Q_ANY && best.slot >= 0) st.node = -1;
 }
 
-// the whole tree again without a stack (after a lost push): children in fixed order, up through the parent links.
-// phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
+// the whole tree again without a stack (after a lost push): tr_rewalk(b, tr_range_probe<Q>{b, r, lo, hi, best}) -- a child is
+// culled as in the walk, a leaf is tested and what it parked decided at once
 template <int Q>
-TR_HD void tr_range_rewalk(const tr_bvh_view& b, const tr_ray& r, float lo, float hi, tr_range_best& best) {
-    const float cut = lo * TR_RANGE_LO_CUT;
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (Q == TR_Q_ANY && best.slot >= 0) break;
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
+struct tr_range_probe {
+    const tr_bvh_view& b;
+    const tr_ray& r;
+    float lo, hi;
+    tr_range_best& best;
+    TR_HDM bool done() const { return Q == TR_Q_ANY && best.slot >= 0; }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
         const tr_f4* q = reinterpret_cast<const tr_f4*>(b.nodes + node);
         const tr_f4 n0 = q[0], n1 = q[1], n2 = q[2], n3 = q[3];
         float tn0, tf0, tn1, tf1;
         tr_node_slabs(r, n0, n1, n2, tn0, tf0, tn1, tf1);
-        const int32_t c = (int32_t)tr_f2u(phase ? n3.y : n3.x);
-        const float tn = phase ? tn1 : tn0, tf = phase ? tf1 : tf0;
-        phase++;
-        if (!tr_range_box(tn, tf, tr_range_limit(hi, best), cut)) continue;
-        if (c < 0) {
-            int32_t pe = -1;
-            tr_range_leaf(b, r, lo, hi, ~c, best, pe);
-            tr_range_drain(b, r, lo, hi, pe, best);
-        } else {
-            node = c;
-            phase = 0;
-        }
+        c = (int32_t)tr_f2u(phase ? n3.y : n3.x);
+        return tr_range_box(phase ? tn1 : tn0, phase ? tf1 : tf0, tr_range_limit(hi, best), lo * TR_RANGE_LO_CUT);
     }
-}
+    TR_HDM void leaf(int32_t slot) const {
+        int32_t pe = -1;
+        tr_range_leaf(b, r, lo, hi, slot, best, pe);
+        tr_range_drain(b, r, lo, hi, pe, best);
+    }
+};
 
 // the outputs of a ray from its best hit (valid = a ray that can hit; best.slot < 0: a miss).  Any pointer may be null.
 TR_HD void tr_range_outputs(const tr_bvh_view& b, const tr_ray& r, bool valid, const tr_range_best& best, uint8_t* hit,
@@ -319,7 +308,7 @@ TR_HD void tr_range_query(const tr_bvh_view& b, float ox, float oy, float oz, fl
         st.node = 0; st.sp = 0; st.pe0 = -1; st.pe1 = -1;
         while (st.node >= 0) tr_range_visit<Q>(b, r, lo, hi, st, best, stack, cap2);
         if (lost) *lost = tr_range_lost(st.sp) ? 1 : 0;
-        if (tr_range_lost(st.sp)) tr_range_rewalk<Q>(b, r, lo, hi, best);
+        if (tr_range_lost(st.sp)) tr_rewalk(b, tr_range_probe<Q>{b, r, lo, hi, best});
     } else if (valid) {
         tr_counters* nc = nullptr;
         const tr_tri w = tr_load_tri<false, false>(b, 0, nc);      // no hierarchy below two triangles

@@ -61,7 +61,7 @@
 //   So G after all instances is the lexicographic minimum of rule 6, whatever the order and whatever was culled.
 //   any: B starts empty for every instance (G is +Inf until the ray's first hit, and the ray is finished by it).
 //
-// THE WALK of an instance is tr_range.h's: tr_range_visit from the member's root, tr_range_rewalk for a lane whose stack
+// THE WALK of an instance is tr_range.h's: tr_range_visit from the member's root, tr_rewalk (tr_range_probe) for a lane whose stack
 // overflowed IN THAT INSTANCE (before the next instance is begun), the one triangle directly below two.  The first visit
 // tests the root's two child boxes against the object-space ray with the proven slab test: that is the cull of an instance.
 // There is no world-space box and no top-level hierarchy: see DESIGN.md 4.6 for what that would have to prove.
@@ -236,7 +236,7 @@ TR_HD void tr_scene_query(const tr_scene_member* members, const tr_scene_inst* i
             while (st.node >= 0) tr_range_visit<Q>(b, r, lo, hi, st, best, stack, cap2);
             if (tr_range_lost(st.sp)) {
                 if (lost) *lost = 1;
-                tr_range_rewalk<Q>(b, r, lo, hi, best);
+                tr_rewalk(b, tr_range_probe<Q>{b, r, lo, hi, best});
             }
         } else {
             tr_scene_single(b, r, lo, hi, best);

@@ -44,10 +44,10 @@
 // lane); below two triangles the one triangle is tested directly.
 // OVERFLOW.  A lane remembers c0 = acc.count before an instance.  If the stack lost a push IN THAT INSTANCE and the rows are
 // not yet full, it sets acc.count = c0 -- dropping what it found in this instance, and nothing else -- and runs
-// tr_cross_rewalk on that instance only, before the next instance is begun.  Crossings of earlier instances are never
+// tr_rewalk (tr_cross_probe) on that instance only, before the next instance is begun.  Crossings of earlier instances are never
 // dropped or recounted; within the instance each walk visits a node at most once, so nothing is counted twice.
 // FILL.  After each instance the lane writes instance[c0 .. min(acc.count, acc.limit)) = k beside the (face, t, slot) that
-// tr_cross_record wrote there: never beyond the rows tr_cross_limit(count[i], offsets[i], total) names, whatever the walk
+// tr_cross_record wrote there: never beyond the rows tr_rows_limit(count[i], offsets[i], total) names, whatever the walk
 // finds, and the ray is finished once they are full.
 // ROWS (tr_scene_cross_rows) then orders the m rows of a ray in place -- a heapsort on (t, instance, face) that carries t,
 // instance, face and slot together; no scratch, and every index it forms is below m whatever the rows hold, NaN keys
@@ -73,31 +73,20 @@ TR_HD void tr_scene_cross_single(const tr_bvh_view& b, const tr_ray& r, float lo
     if (tr_range_tri(r, w.ax, w.ay, w.az, w.bx, w.by, w.bz, w.cx, w.cy, w.cz, lo, hi, tt)) tr_cross_record<MODE>(acc, w.face, tt, 0);
 }
 
-// m rows into ascending (t, instance, face) order, in place; s (the slots beside them) may be null.  tr_cross_sort with one
-// more key: the comparisons only choose between indices already bounded by `end`.
-TR_HD void tr_scene_cross_swap(float* t, int32_t* in, int32_t* f, int32_t* s, int32_t i, int32_t j) {
-    const int32_t a = in[i]; in[i] = in[j]; in[j] = a;
-    tr_cross_swap(t, f, s, i, j);
-}
-TR_HD bool tr_scene_cross_before(const float* t, const int32_t* in, const int32_t* f, int32_t i, int32_t j) {
-    return t[i] < t[j] || (t[i] == t[j] && (in[i] < in[j] || (in[i] == in[j] && f[i] < f[j])));
-}
-TR_HD void tr_scene_cross_sift(float* t, int32_t* in, int32_t* f, int32_t* s, int32_t root, int32_t end) {
-    for (;;) {
-        int32_t child = 2 * root + 1;
-        if (child >= end) break;
-        if (child + 1 < end && tr_scene_cross_before(t, in, f, child, child + 1)) child++;
-        if (!tr_scene_cross_before(t, in, f, root, child)) break;
-        tr_scene_cross_swap(t, in, f, s, root, child);
-        root = child;
+// m rows into ascending (t, instance, face) order, in place (tr_rows_sort); s (the slots beside them) may be null
+struct tr_scene_cross_sorted {
+    int32_t* in;
+    tr_cross_sorted r;
+    TR_HDM bool before(int32_t i, int32_t j) const {
+        return r.t[i] < r.t[j] || (r.t[i] == r.t[j] && (in[i] < in[j] || (in[i] == in[j] && r.f[i] < r.f[j])));
     }
-}
+    TR_HDM void swap(int32_t i, int32_t j) const {
+        const int32_t a = in[i]; in[i] = in[j]; in[j] = a;
+        r.swap(i, j);
+    }
+};
 TR_HD void tr_scene_cross_sort(float* t, int32_t* in, int32_t* f, int32_t* s, int32_t m) {
-    for (int32_t i = m / 2 - 1; i >= 0; i--) tr_scene_cross_sift(t, in, f, s, i, m);
-    for (int32_t end = m - 1; end > 0; end--) {
-        tr_scene_cross_swap(t, in, f, s, 0, end);
-        tr_scene_cross_sift(t, in, f, s, 0, end);
-    }
+    tr_rows_sort(tr_scene_cross_sorted{in, {t, f, s}}, m);
 }
 
 // order the m rows of a world ray and evaluate the optional outputs of each (slot is required for front / loc3 / uv2) as
@@ -149,11 +138,11 @@ TR_HD int32_t tr_scene_cross_query(const tr_scene_member* members, const tr_scen
             tr_cross_state st;
             st.node = 0; st.sp = 0; st.pe0 = -1; st.pe1 = -1;
             while (st.node >= 0) tr_cross_visit<MODE>(b, r, lo, hi, st, acc, stack, cap2);
-            if (tr_cross_lost(st.sp)) {
+            if (tr_walk_lost(st.sp)) {
                 if (lost) *lost = 1;
                 if (!tr_cross_full<MODE>(acc)) {
                     acc.count = c0;
-                    tr_cross_rewalk<MODE>(b, r, lo, hi, acc);
+                    tr_rewalk(b, tr_cross_probe<MODE>{b, r, lo, hi, acc});
                 }
             }
         } else {

@@ -85,7 +85,7 @@
 // walk culls from its first node -- then tr_scene_near_visit from the member's root, whose first visit tests the placed boxes
 // of the root's children against G: that is the cull of an instance.  The {node, float32 bound rounded down} entries, the push
 // and the pop are tr_near_push / tr_near_pop as they are.  A lane whose stack overflowed IN THAT INSTANCE walks it again without
-// a stack (tr_scene_near_rewalk) before the next instance is begun.  Below two triangles the one triangle is tested directly.
+// a stack (tr_rewalk on a tr_scene_near_probe) before the next instance is begun.  Below two triangles the one triangle is tested directly.
 // The loop over instances is linear: there is no structure over them.
 #pragma once
 #include "tr_scene.h"
@@ -218,31 +218,20 @@ TR_HD int32_t tr_scene_near_seed(const tr_bvh_view& b, const tr_scene_near_map& 
     return -1;
 }
 
-// the whole member again without a stack (after a lost push): tr_near_rewalk with the placed bound and placed leaves
-TR_HD void tr_scene_near_rewalk(const tr_bvh_view& b, const tr_scene_near_map& A, float px, float py, float pz, tr_near_best& best) {
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
+// the whole member again without a stack (after a lost push): tr_near_probe with the placed bound and placed leaves
+struct tr_scene_near_probe {
+    const tr_bvh_view& b;
+    const tr_scene_near_map& A;
+    float px, py, pz;
+    tr_near_best& best;
+    TR_HDM bool done() const { return false; }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
         const tr_near_node n = tr_scene_near_load(b, A, node, px, py, pz);
-        const int32_t c = phase ? n.c1 : n.c0;
-        const double lb = phase ? n.lb1 : n.lb0;
-        phase++;
-        if (lb > best.d2) continue;
-        if (c < 0) {
-            tr_scene_near_leaf(b, A, ~c, px, py, pz, best);
-        } else {
-            node = c;
-            phase = 0;
-        }
+        c = phase ? n.c1 : n.c0;
+        return !((phase ? n.lb1 : n.lb0) > best.d2);
     }
-}
+    TR_HDM void leaf(int32_t slot) const { tr_scene_near_leaf(b, A, slot, px, py, pz, best); }
+};
 
 // the four outputs of a point from the best placed triangle (valid: the query can accept something; g.slot < 0: nothing was
 // accepted).  Any of the pointers may be null.
@@ -277,7 +266,7 @@ TR_HD void tr_scene_near_instance(const tr_bvh_view& b, const tr_scene_near_map&
         while (st.node >= 0) tr_scene_near_visit(b, A, px, py, pz, st, best, stack, cap2);
         if (tr_near_lost(st.sp)) {
             if (lost) *lost = 1;
-            tr_scene_near_rewalk(b, A, px, py, pz, best);
+            tr_rewalk(b, tr_scene_near_probe{b, A, px, py, pz, best});
         }
     } else {
         tr_scene_near_leaf(b, A, 0, px, py, pz, best);      // no hierarchy below two triangles

@@ -29,7 +29,7 @@
 //      any   = uint8: the point is inside some instance.
 //      count = int32: the number of instances it is inside.
 //      list  = the indices of those instances, ascending, uncapped, at rows offsets[i] .. offsets[i] + count[i] (int64
-//              offsets: tr_hits_scan); the rows a point may write are tr_cross_limit(count[i], offsets[i], total).
+//              offsets: tr_hits_scan); the rows a point may write are tr_rows_limit(count[i], offsets[i], total).
 //    Every element of every output is written.  Everything is a pure function of (p, d, instances, member triangles): it
 //    depends neither on the order in which instances or nodes are visited, nor on stack capacity, nor on launch shape, and
 //    is bit-comparable with cross_sim.brute per instance on the rays of scene_sim.transform and a parity in numpy.
@@ -46,10 +46,10 @@
 // tr_cross.h (node ids only, TR_CROSS_STACK of them per lane) and a tr_cross_acc OF ITS OWN: the counter is per instance and
 // per pass, not the ray-wide accumulator of tr_scene_cross_query.  Below two triangles the one triangle is tested directly
 // (tr_scene_cross_single).
-// OVERFLOW.  A lane whose stack lost a push in a pass drops THAT PASS'S count -- nothing else -- and runs tr_cross_rewalk for
+// OVERFLOW.  A lane whose stack lost a push in a pass drops THAT PASS'S count -- nothing else -- and runs tr_rewalk (tr_cross_probe) for
 // that pass only, before the next pass or instance is begun: the c0 rule of tr_scene_cross.h with c0 = 0.
 // MODES.  ANY: a point that has found an instance is finished.  FILL: a containing instance is written into the point's
-// rows as it is found, never beyond the rows tr_cross_limit names; the point is finished once they are full.  The kernel
+// rows as it is found, never beyond the rows tr_rows_limit names; the point is finished once they are full.  The kernel
 // visits instances in ascending order, so its rows are ascending as written; the host query, which may visit in any
 // `order`, sorts its rows afterwards (tr_scene_points_sort).  Misdirected counts or offsets give wrong rows, never a write
 // outside the arrays.
@@ -118,10 +118,10 @@ TR_HD int32_t tr_scene_points_pass(const tr_bvh_view& b, const tr_ray& r, const 
         tr_cross_state st;
         st.node = 0; st.sp = 0; st.pe0 = -1; st.pe1 = -1;
         while (st.node >= 0) tr_cross_visit<TR_CROSS_COUNT>(b, r, lo, hi, st, ca, stack, cap2);
-        if (tr_cross_lost(st.sp)) {
+        if (tr_walk_lost(st.sp)) {
             if (lost) *lost = 1;
             ca.count = 0;
-            tr_cross_rewalk<TR_CROSS_COUNT>(b, r, lo, hi, ca);
+            tr_rewalk(b, tr_cross_probe<TR_CROSS_COUNT>{b, r, lo, hi, ca});
         }
     } else {
         tr_scene_cross_single<TR_CROSS_COUNT>(b, r, lo, hi, ca);

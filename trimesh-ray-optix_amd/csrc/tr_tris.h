@@ -1,6 +1,6 @@
 // tr_tris.h -- triangle queries (include/triro_tris.h): the faces of a mesh that meet a triangle, the narrow phase of mesh
 // against mesh.  Host + device, as tr_boxes.h, whose culling (tr_box_apart, tr_boxes_load), result record (tr_boxes_acc,
-// tr_boxes_full) and -- through tr_within.h -- stack, row limit and ordering it uses UNCHANGED: k_tris<> and k_tris_rows
+// tr_set_probe) and -- through tr_within.h and tr_walk.h -- stack, row limit and ordering it uses UNCHANGED: k_tris<> and k_tris_rows
 // (tris.hip) instantiate the walk per lane, tests/host_sim/tris_sim.cpp compiles the very same functions with g++.  Not a CPU
 // fallback: nothing in the C ABI reaches the host instantiation.
 //
@@ -58,14 +58,9 @@
 // step 1 of the predicate separates it, with the same exact comparisons.  A skipped subtree holds no face that meets Q.  No
 // rounding argument.
 //
-// THE WALK is the set walk of tr_boxes.h (tr_boxes_load on Q's box, the state and stack of tr_within.h) with this leaf: one
-// 64-byte node per visit, both child boxes tested, leaf children that survive evaluated and recorded (FILL), counted (COUNT)
-// or ending the walk (ANY); of the internal children that survive, child 0 is visited next and child 1 pushed.  Stack entries
-// are NODE IDS ONLY, TR_TRIS_STACK = 32 per lane, a column of LDS; a push that does not fit sets the sticky lost bit, and a
-// lane that ends with it set DISCARDS its partial count / write cursor and repeats the walk without a stack through the parent
-// links (tr_tris_rewalk).  Each walk visits a node at most once: nothing is counted twice.  Below two triangles there is no
-// hierarchy: the one triangle is tested directly.
-// FILL writes, in walk order and never beyond `limit` = tr_within_limit(count, offset, total) rows, the face index itself (no
+// THE WALK is the set walk of tr_boxes.h on Q's box (tr_set_probe; THE SET WALK of tr_walk.h) with this leaf;
+// TR_TRIS_STACK = 32 node ids per lane.
+// FILL writes, in walk order and never beyond `limit` = tr_rows_limit(count, offset, total) rows, the face index itself (no
 // flag rides along: the rows are plain face indices); tr_tris_rows then orders the segment (tr_within_sort).
 //
 // REGISTERS.  The float64 part never holds the seventeen axes: tr_tris_sat keeps the frame (e0, -e2, dp, dq, dr), the edges
@@ -178,94 +173,33 @@ TR_HD bool tr_tris_meets(const tr_tris_q& q, const tr_box& qb, float axf, float 
     return tr_tris_sat(q, axf, ayf, azf, bxf, byf, bzf, cxf, cyf, czf);
 }
 
-// one face against the query
+// one face against the query (qb = tr_tris_box(q)): the leaf of the set walk of tr_boxes.h on qb
 template <int MODE>
-TR_HD void tr_tris_leaf(const tr_bvh_view& b, int32_t slot, const tr_tris_q& q, const tr_box& qb, tr_boxes_acc& acc) {
-    tr_counters* nc = nullptr;
-    const tr_tri t = tr_load_tri<false, false>(b, slot, nc);
-    if (tr_near_active(t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz) &&
-        tr_tris_meets(q, qb, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz)) {
-        if (MODE == TR_TRIS_FILL && acc.count < acc.limit) acc.key[acc.count] = t.face;
-        acc.count++;
-    }
-}
-
-// visit st.node (>= 0): see THE WALK
-template <int MODE>
-TR_HD void tr_tris_visit(const tr_bvh_view& b, const tr_tris_q& q, const tr_box& qb, tr_within_state& st, tr_boxes_acc& acc,
-                         const tr_ring stack, uint32_t cap2) {
-    const tr_boxes_node n = tr_boxes_load(b, st.node, qb);
-#pragma unroll 1
-    for (int k = 0; k < 2; k++) {
-        const int32_t c = k ? n.c1 : n.c0;
-        const bool apart = k ? n.apart1 : n.apart0;
-        if (c < 0 && !apart && !tr_boxes_full<MODE>(acc)) tr_tris_leaf<MODE>(b, ~c, q, qb, acc);
-    }
-    if (tr_boxes_full<MODE>(acc)) { st.node = -1; return; }
-    const bool go0 = n.c0 >= 0 && !n.apart0, go1 = n.c1 >= 0 && !n.apart1;
-    if (go0) {
-        if (go1) tr_within_push(stack, cap2, st.sp, n.c1);
-        st.node = n.c0;
-    } else if (go1) {
-        st.node = n.c1;
-    } else {
-        st.node = tr_within_pop(stack, st.sp);
-    }
-}
-
-// the whole tree again without a stack (after a lost push; the caller has reset acc.count): children in fixed order, up
-// through the parent links.  phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
-template <int MODE>
-TR_HD void tr_tris_rewalk(const tr_bvh_view& b, const tr_tris_q& q, const tr_box& qb, tr_boxes_acc& acc) {
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (tr_boxes_full<MODE>(acc)) break;
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
-        const tr_boxes_node n = tr_boxes_load(b, node, qb);
-        const int32_t c = phase ? n.c1 : n.c0;
-        const bool apart = phase ? n.apart1 : n.apart0;
-        phase++;
-        if (apart) continue;
-        if (c < 0) {
-            tr_tris_leaf<MODE>(b, ~c, q, qb, acc);
-        } else {
-            node = c;
-            phase = 0;
+struct tr_tris_leaf {
+    const tr_bvh_view& b;
+    const tr_tris_q& q;
+    const tr_box& qb;
+    TR_HDM void operator()(int32_t slot, tr_boxes_acc& acc) const {
+        tr_counters* nc = nullptr;
+        const tr_tri t = tr_load_tri<false, false>(b, slot, nc);
+        if (tr_near_active(t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz) &&
+            tr_tris_meets(q, qb, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz)) {
+            if (MODE == TR_TRIS_FILL && acc.count < acc.limit) acc.key[acc.count] = t.face;
+            acc.count++;
         }
     }
+};
+template <int MODE>
+TR_HD tr_set_probe<MODE, tr_tris_leaf<MODE>> tr_tris_probe(const tr_bvh_view& b, const tr_tris_q& q, const tr_box& qb, tr_boxes_acc& acc) {
+    return {b, qb, {b, q, qb}, acc};
 }
 
 // order the m rows of a query: plain face indices, ascending
 TR_HD void tr_tris_rows(int32_t* face, int32_t m) { tr_within_sort(face, nullptr, m); }
 
-// one query, start to end, on one lane (the host simulation; the kernel runs the first walk as a wave loop).
-// stack_entries: 1 .. TR_TRIS_STACK, 0 = all of them.  Returns the number of faces met (FILL: min(it, acc.limit) rows are
-// written and still in walk order); *lost (may be null): the first walk overflowed its stack.
+// one query, start to end, on one lane (the host simulation: tr_set_query); stack_entries: 1 .. TR_TRIS_STACK, 0 = all of them
 template <int MODE>
 TR_HD int32_t tr_tris_query(const tr_bvh_view& b, const tr_tris_q& q, const tr_ring stack, int stack_entries, tr_boxes_acc& acc, bool* lost) {
-    const bool live = tr_tris_live(q) && b.num_tris > 0;
     const tr_box qb = tr_tris_box(q);
-    acc.count = 0;
-    if (lost) *lost = false;
-    if (live && b.num_tris >= 2 && !tr_boxes_full<MODE>(acc)) {
-        const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_TRIS_STACK);
-        tr_within_state st;
-        st.node = 0; st.sp = 0;
-        while (st.node >= 0) tr_tris_visit<MODE>(b, q, qb, st, acc, stack, cap2);
-        if (lost) *lost = tr_within_lost(st.sp);
-        if (tr_within_lost(st.sp) && !tr_boxes_full<MODE>(acc)) {
-            acc.count = 0;
-            tr_tris_rewalk<MODE>(b, q, qb, acc);
-        }
-    } else if (live && !tr_boxes_full<MODE>(acc)) {
-        tr_tris_leaf<MODE>(b, 0, q, qb, acc);      // no hierarchy below two triangles
-    }
-    return acc.count;
+    return tr_set_query(b, tr_tris_probe<MODE>(b, q, qb, acc), tr_tris_live(q), stack, stack_entries, TR_TRIS_STACK, lost);
 }

@@ -27,14 +27,10 @@
 // holds no face with d2 <= R2, a face at exactly r included.  Boxes with NaN or Inf behave as there: a NaN difference
 // selects the bound 0, and nothing exceeds R2 = +Inf.
 //
-// THE SET WALK (tr_within_visit, one node per call, from the root).  Both child boxes are bounded (tr_near_load); children that
-// are leaves are evaluated where their bound does not exceed R2 and recorded (FILL), counted (COUNT) or end the walk (ANY);
-// of the internal children that survive, the nearer is visited next and the other is pushed.  The threshold never moves, so
-// a pushed entry never dies: stack entries are NODE IDS ONLY, 4 bytes, TR_WITHIN_STACK = 32 of them per lane.  A push that
-// does not fit sets the sticky lost bit of st.sp; a lane that ends with it set DISCARDS its partial count / write cursor and
-// repeats the whole walk without a stack, through the parent links (tr_within_rewalk, as tr_near_rewalk): nothing is counted
-// twice.  Each walk visits a node at most once, so the faces one walk records are distinct.  Below two triangles there is no
-// hierarchy: the one triangle is tested directly.
+// THE WALK is THE SET WALK of tr_walk.h (the node-id stack, the re-walk of a lane that lost a push, tr_set_query) with this
+// visit (tr_within_visit): both child boxes are bounded (tr_near_load); children that are leaves are evaluated where their
+// bound does not exceed R2; of the internal children that survive, the nearer is visited next and the other is pushed.  The
+// threshold never moves, so a pushed entry never dies: TR_WITHIN_STACK = 32 node ids per lane.
 // FILL writes the faces of a point in walk order at its rows -- never more than `limit` = the rows the caller's count / offsets
 // / total leave it, whatever the walk finds -- and ends once they are full; tr_within_rows then puts the segment into ascending
 // face order (an in-place heapsort that carries the arena slot beside the face when rows are to be evaluated) and evaluates
@@ -42,14 +38,14 @@
 //
 // THE BOUNDED NEAREST is the walk of tr_nearest.h with one change: the best starts as {d2 = R2, face = INT_MAX, slot = -1}
 // instead of tr_near_init.  tr_near_leaf's comparison then accepts a face at exactly R2 (its index is below INT_MAX) and
-// rejects anything farther; tr_near_seed, tr_near_visit, tr_near_rewalk, tr_near_outputs and the 8-byte {node, bound} entries
+// rejects anything farther; tr_near_seed, tr_near_visit, tr_near_probe, tr_near_outputs and the 8-byte {node, bound} entries
 // are reused unchanged.
 #pragma once
 #include "tr_nearest.h"
 
 #define TR_WITHIN_STACK 32      // node ids per lane: 32 x 4 B x 128 lanes = 16 KB of LDS per workgroup
 
-enum tr_within_mode { TR_WITHIN_ANY = 0, TR_WITHIN_COUNT = 1, TR_WITHIN_FILL = 2 };
+enum tr_within_mode { TR_WITHIN_ANY = TR_SET_ANY, TR_WITHIN_COUNT = TR_SET_COUNT, TR_WITHIN_FILL = TR_SET_FILL };
 
 // what a lane has found: `count` faces, of which the first min(count, limit) were written (FILL)
 struct tr_within_acc {
@@ -58,19 +54,9 @@ struct tr_within_acc {
     int32_t* face;      // FILL: its rows of the face list
     int32_t* slot;      // FILL: its rows of the slot scratch, or null
 };
-struct tr_within_state {
-    int32_t node;    // next internal node to visit, -1 = nothing left
-    uint32_t sp;     // 2 * entries in use | lost
-};
 
 TR_HD bool tr_within_valid(float px, float py, float pz, float r) { return tr_near_valid(px, py, pz) && r >= 0.0f; }
 TR_HD double tr_within_r2(float r) { return (double)r * (double)r; }
-TR_HD bool tr_within_lost(uint32_t sp) { return (sp & 1u) != 0; }
-// the walk has what it came for: ANY a face, FILL all its rows
-template <int MODE>
-TR_HD bool tr_within_full(const tr_within_acc& acc) {
-    return MODE == TR_WITHIN_ANY ? acc.count > 0 : (MODE == TR_WITHIN_FILL ? acc.count >= acc.limit : false);
-}
 
 // one triangle against the radius (a select on activity, as tr_near_leaf: the arithmetic on NaN / Inf is harmless)
 template <int MODE>
@@ -88,25 +74,9 @@ TR_HD void tr_within_leaf(const tr_bvh_view& b, int32_t slot, float px, float py
     }
 }
 
-// Stack: entry e of a lane is word e of its column of a tr_ring.  cap2 = 2 * entries the walk may use.
-TR_HD void tr_within_push(const tr_ring stack, uint32_t cap2, uint32_t& sp, int32_t node) {
-    const uint32_t w = sp & ~1u;
-    if (w < cap2) {
-        tr_ring_put(stack, w >> 1, node);
-        sp += 2u;
-    } else {
-        sp |= 1u;
-    }
-}
-TR_HD int32_t tr_within_pop(const tr_ring stack, uint32_t& sp) {
-    if (sp < 2u) return -1;
-    sp -= 2u;
-    return tr_ring_get(stack, sp >> 1);
-}
-
-// visit st.node (>= 0): see THE SET WALK
+// visit st.node (>= 0): see THE WALK
 template <int MODE>
-TR_HD void tr_within_visit(const tr_bvh_view& b, float px, float py, float pz, double R2, tr_within_state& st, tr_within_acc& acc,
+TR_HD void tr_within_visit(const tr_bvh_view& b, float px, float py, float pz, double R2, tr_walk_state& st, tr_within_acc& acc,
                            const tr_ring stack, uint32_t cap2) {
     const tr_near_node n = tr_near_load(b, st.node, px, py, pz);
     const bool swap = n.lb1 < n.lb0;
@@ -116,79 +86,53 @@ TR_HD void tr_within_visit(const tr_bvh_view& b, float px, float py, float pz, d
     for (int k = 0; k < 2; k++) {
         const int32_t c = k ? cf : cn;
         const double lb = k ? lf : ln;
-        if (c < 0 && !(lb > R2) && !tr_within_full<MODE>(acc)) tr_within_leaf<MODE>(b, ~c, px, py, pz, R2, acc);
+        if (c < 0 && !(lb > R2) && !tr_set_full<MODE>(acc)) tr_within_leaf<MODE>(b, ~c, px, py, pz, R2, acc);
     }
-    if (tr_within_full<MODE>(acc)) { st.node = -1; return; }
+    if (tr_set_full<MODE>(acc)) { st.node = -1; return; }
     const bool go_n = cn >= 0 && !(ln > R2), go_f = cf >= 0 && !(lf > R2);
     if (go_n) {
-        if (go_f) tr_within_push(stack, cap2, st.sp, cf);
+        if (go_f) tr_walk_push(stack, cap2, st.sp, cf);
         st.node = cn;
     } else if (go_f) {
         st.node = cf;
     } else {
-        st.node = tr_within_pop(stack, st.sp);
+        st.node = tr_walk_pop(stack, st.sp);
     }
 }
 
-// the whole tree again without a stack (after a lost push; the caller has reset acc.count): children in fixed order, up
-// through the parent links.  phase 0: arriving from above (child 0 next), 1: child 0 done (child 1 next), 2: both done (climb)
+// the query as tr_walk.h sees it (tr_rewalk, tr_set_query, tr_set_kernel)
 template <int MODE>
-TR_HD void tr_within_rewalk(const tr_bvh_view& b, float px, float py, float pz, double R2, tr_within_acc& acc) {
-    int32_t node = 0;
-    int phase = 0;
-    for (;;) {
-        if (tr_within_full<MODE>(acc)) break;
-        if (phase == 2) {
-            const int32_t parent = b.links[node].parent;
-            if (parent < 0) break;
-            phase = b.nodes[parent].c0 == node ? 1 : 2;
-            node = parent;
-            continue;
-        }
+struct tr_within_probe {
+    const tr_bvh_view& b;
+    float px, py, pz;
+    double R2;
+    tr_within_acc& acc;
+    TR_HDM bool done() const { return tr_set_full<MODE>(acc); }
+    TR_HDM void leaf(int32_t slot) const { tr_within_leaf<MODE>(b, slot, px, py, pz, R2, acc); }
+    TR_HDM bool child(int32_t node, int phase, int32_t& c) const {
         const tr_near_node n = tr_near_load(b, node, px, py, pz);
-        const int32_t c = phase ? n.c1 : n.c0;
-        const double lb = phase ? n.lb1 : n.lb0;
-        phase++;
-        if (lb > R2) continue;
-        if (c < 0) {
-            tr_within_leaf<MODE>(b, ~c, px, py, pz, R2, acc);
-        } else {
-            node = c;
-            phase = 0;
-        }
+        c = phase ? n.c1 : n.c0;
+        return !((phase ? n.lb1 : n.lb0) > R2);
     }
-}
+    TR_HDM void visit(tr_walk_state& st, const tr_ring stack, uint32_t cap2) const {
+        tr_within_visit<MODE>(b, px, py, pz, R2, st, acc, stack, cap2);
+    }
+};
 
-// the rows a point may write: [off, off + count) cut to [0, total); nothing for a negative count or an offset outside
-TR_HD int32_t tr_within_limit(int32_t count, int64_t off, int64_t total) {
-    if (count <= 0 || off < 0 || off >= total) return 0;
-    const int64_t room = total - off;
-    return (int64_t)count < room ? count : (int32_t)room;
-}
+// the rows a point may write: tr_rows_limit under the name the host simulations of within, boxes, tris and planes call
+TR_HD int32_t tr_within_limit(int32_t count, int64_t off, int64_t total) { return tr_rows_limit(count, off, total); }
 
-// m rows into ascending face order, in place; s (the slots beside the faces) may be null.  A heapsort: no scratch, and every
-// index it forms is below m whatever the rows hold.
-TR_HD void tr_within_swap(int32_t* f, int32_t* s, int32_t i, int32_t j) {
-    const int32_t a = f[i]; f[i] = f[j]; f[j] = a;
-    if (s) { const int32_t c = s[i]; s[i] = s[j]; s[j] = c; }
-}
-TR_HD void tr_within_sift(int32_t* f, int32_t* s, int32_t root, int32_t end) {
-    for (;;) {
-        int32_t child = 2 * root + 1;
-        if (child >= end) break;
-        if (child + 1 < end && f[child] < f[child + 1]) child++;
-        if (!(f[root] < f[child])) break;
-        tr_within_swap(f, s, root, child);
-        root = child;
+// m rows into ascending face order, in place (tr_rows_sort); s (the slots beside the faces) may be null
+struct tr_within_sorted {
+    int32_t* f;
+    int32_t* s;
+    TR_HDM bool before(int32_t i, int32_t j) const { return f[i] < f[j]; }
+    TR_HDM void swap(int32_t i, int32_t j) const {
+        const int32_t a = f[i]; f[i] = f[j]; f[j] = a;
+        if (s) { const int32_t c = s[i]; s[i] = s[j]; s[j] = c; }
     }
-}
-TR_HD void tr_within_sort(int32_t* f, int32_t* s, int32_t m) {
-    for (int32_t i = m / 2 - 1; i >= 0; i--) tr_within_sift(f, s, i, m);
-    for (int32_t end = m - 1; end > 0; end--) {
-        tr_within_swap(f, s, 0, end);
-        tr_within_sift(f, s, 0, end);
-    }
-}
+};
+TR_HD void tr_within_sort(int32_t* f, int32_t* s, int32_t m) { tr_rows_sort(tr_within_sorted{f, s}, m); }
 
 // order the m rows of a point and evaluate the optional outputs of each (slot is required for them): as tr_near_outputs
 TR_HD void tr_within_rows(const tr_bvh_view& b, float px, float py, float pz, int32_t* face, int32_t* slot, int32_t m, float* distance,
@@ -206,30 +150,12 @@ TR_HD void tr_within_rows(const tr_bvh_view& b, float px, float py, float pz, in
     }
 }
 
-// one point, start to end, on one lane (the host simulation; the kernel runs the first walk as a wave loop).
-// stack_entries: 1 .. TR_WITHIN_STACK, 0 = all of them.  Returns the number of faces within (FILL: min(it, acc.limit) rows are
-// written and still in walk order); *lost (may be null): the first walk overflowed its stack.
+// one point, start to end, on one lane (the host simulation: tr_set_query); stack_entries: 1 .. TR_WITHIN_STACK, 0 = all of them
 template <int MODE>
 TR_HD int32_t tr_within_query(const tr_bvh_view& b, float px, float py, float pz, float r, const tr_ring stack, int stack_entries,
                               tr_within_acc& acc, bool* lost) {
-    const bool valid = tr_within_valid(px, py, pz, r) && b.num_tris > 0;
-    const double R2 = tr_within_r2(r);
-    acc.count = 0;
-    if (lost) *lost = false;
-    if (valid && b.num_tris >= 2 && !tr_within_full<MODE>(acc)) {
-        const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_WITHIN_STACK);
-        tr_within_state st;
-        st.node = 0; st.sp = 0;
-        while (st.node >= 0) tr_within_visit<MODE>(b, px, py, pz, R2, st, acc, stack, cap2);
-        if (lost) *lost = tr_within_lost(st.sp);
-        if (tr_within_lost(st.sp) && !tr_within_full<MODE>(acc)) {
-            acc.count = 0;
-            tr_within_rewalk<MODE>(b, px, py, pz, R2, acc);
-        }
-    } else if (valid && !tr_within_full<MODE>(acc)) {
-        tr_within_leaf<MODE>(b, 0, px, py, pz, R2, acc);      // no hierarchy below two triangles
-    }
-    return acc.count;
+    const tr_within_probe<MODE> probe = {b, px, py, pz, tr_within_r2(r), acc};
+    return tr_set_query(b, probe, tr_within_valid(px, py, pz, r), stack, stack_entries, TR_WITHIN_STACK, lost);
 }
 
 // the bounded nearest: where the best starts (see THE BOUNDED NEAREST)
@@ -247,7 +173,7 @@ TR_HD void tr_within_closest_query(const tr_bvh_view& b, float px, float py, flo
         for (int32_t node = 0; node >= 0;) node = tr_near_seed(b, node, px, py, pz, best);
         st.node = 0; st.sp = 0;
         while (st.node >= 0) tr_near_visit(b, px, py, pz, st, best, stack, cap2);
-        if (tr_near_lost(st.sp)) tr_near_rewalk(b, px, py, pz, best);
+        if (tr_near_lost(st.sp)) tr_rewalk(b, tr_near_probe{b, px, py, pz, best});
     } else if (valid) {
         tr_near_leaf(b, 0, px, py, pz, best);
     }

@@ -1,13 +1,13 @@
 // tris.hip -- libtriro_tris.so (include/triro_tris.h): the faces that meet each query triangle.
 //
-// The contract, the culling proof and the walk are csrc/tr_tris.h (host + device) on the culling of csrc/tr_boxes.h and the
-// stack, the row limit and the ordering of csrc/tr_within.h; this file is the wave loop around tr_tris_visit, the launches and
-// the C entries.
+// The contract, the culling proof and the walk are csrc/tr_tris.h (host + device) on the box-culled set walk of csrc/tr_boxes.h
+// and csrc/tr_walk.h and the ordering of csrc/tr_within.h; this file is the query load, the launches and the C entries (the
+// kernel body: tr_set_kernel).
 //
 //  * One query triangle per lane, block k takes triangles 128 k ... 128 k + 127 (64-bit index math), shaped like k_boxes.
 //  * k_tris<ANY | COUNT | FILL>: the stack of a lane is a column of LDS, TR_TRIS_STACK = 32 node ids, 16 KB per workgroup.
 //    The box of the query is computed once per lane.  A lane whose stack overflowed drops what it found and walks the tree
-//    again without one (tr_tris_rewalk) after the wave's loop.  FILL leaves the rows of a query as face indices in walk order;
+//    again without one (tr_rewalk) after the wave's loop.  FILL leaves the rows of a query as face indices in walk order;
 //    k_tris_rows (no LDS) orders them.
 #include <string>
 
@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int TQ_BS = 128;      // one query triangle per lane, two waves per workgroup
+constexpr int TQ_BS = TR_LANE_BS;      // one query triangle per lane, two waves per workgroup
 
 struct tq_query {
     tr_tris_q q;
@@ -41,7 +41,7 @@ __device__ __forceinline__ tq_query tq_load(const tr_bvh_view& b, const float* _
 }  // namespace
 
 // ANY: out8[i] = 0 / 1.  COUNT: out32[i] = the number of faces met.  FILL: the faces of query i, in walk order, at rows
-// offsets[i] .. of face, at most tr_within_limit of them.
+// offsets[i] .. of face, at most tr_rows_limit of them.
 template <int MODE>
 __global__ __launch_bounds__(TQ_BS) void k_tris(tr_bvh_view b, const float* __restrict__ tri, int64_t n, uint8_t* __restrict__ out8,
                                                 int32_t* __restrict__ out32, const int32_t* __restrict__ count,
@@ -52,34 +52,9 @@ __global__ __launch_bounds__(TQ_BS) void k_tris(tr_bvh_view b, const float* __re
     const tr_ring stack = {stack_lds + threadIdx.x, TQ_BS};
     const int64_t i = (int64_t)blockIdx.x * TQ_BS + threadIdx.x;
     const tq_query q = tq_load(b, tri, n, i);
-    tr_boxes_acc acc;
-    acc.count = 0; acc.limit = 0; acc.key = nullptr;
-    if (MODE == TR_TRIS_FILL && q.in_range) {
-        const int64_t off = offsets[i];
-        acc.limit = tr_within_limit(count[i], off, total);
-        if (acc.limit > 0) acc.key = face + off;
-    }
-    const bool walk = q.live && !tr_boxes_full<MODE>(acc);      // (FILL: a query without rows has nothing to do)
-    if (b.num_tris >= 2) {      // (wave-uniform)
-        const uint32_t cap2 = 2u * (uint32_t)(stack_entries > 0 ? stack_entries : TR_TRIS_STACK);
-        tr_within_state st;
-        st.node = walk ? 0 : -1; st.sp = 0;
-        for (;;) {
-            if (!TR_WAVE_ANY(st.node >= 0)) break;
-            if (st.node >= 0) tr_tris_visit<MODE>(b, q.q, q.box, st, acc, stack, cap2);
-            TR_CONVERGE();
-        }
-        if (tr_within_lost(st.sp) && !tr_boxes_full<MODE>(acc)) {      // cold: the partial result is dropped, not added to
-            acc.count = 0;
-            tr_tris_rewalk<MODE>(b, q.q, q.box, acc);
-        }
-    } else if (walk) {
-        tr_tris_leaf<MODE>(b, 0, q.q, q.box, acc);      // no hierarchy below two triangles
-    }
-    if (q.in_range) {
-        if (MODE == TR_TRIS_ANY) out8[i] = acc.count > 0 ? 1 : 0;
-        if (MODE == TR_TRIS_COUNT) out32[i] = acc.count;
-    }
+    tr_boxes_acc acc = {0, 0, nullptr};
+    tr_set_kernel<MODE, TR_TRIS_STACK>(b, tr_tris_probe<MODE>(b, q.q, q.box, acc), stack, q.live, q.in_range, i, count, offsets, total,
+                                       [&](int64_t off) { acc.key = face + off; }, stack_entries, out8, out32);
 }
 
 // after k_tris<FILL>: the rows of query i into ascending face order
@@ -88,7 +63,7 @@ __global__ __launch_bounds__(TQ_BS) void k_tris_rows(int64_t n, const int32_t* _
     const int64_t i = (int64_t)blockIdx.x * TQ_BS + threadIdx.x;
     if (i >= n) return;
     const int64_t off = offsets[i];
-    const int32_t m = tr_within_limit(count[i], off, total);
+    const int32_t m = tr_rows_limit(count[i], off, total);
     if (m <= 0) return;
     tr_tris_rows(face + off, m);
 }
@@ -97,27 +72,13 @@ namespace {
 
 // the checks every entry shares; nblocks comes back
 int tq_check(const tr_bvh* bvh, const float* d_tri, int64_t n, const void* d_required, int stack_entries, int64_t& nblocks) {
-    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
-    if (n < 0) return tr_fail(TR_ERR_INVALID_ARG, "n < 0");
-    if (stack_entries < 0 || stack_entries > TR_TRIS_STACK)
-        return tr_fail(TR_ERR_INVALID_ARG, "stack_entries must be 0 (all) or 1 .. " + std::to_string(TR_TRIS_STACK));
-    if (n > 0 && (!d_tri || !d_required)) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
-    nblocks = (n + TQ_BS - 1) / TQ_BS;
-    if (nblocks > 0x7fffffffll) return tr_fail(TR_ERR_INVALID_ARG, "too many triangles for one launch");
-    return TR_OK;
-}
-
-tr_bvh_view tq_view(const tr_bvh* bvh) {
-    tr_bvh_view view;
-    view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
-    view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
-    return view;
+    return tr_lane_check(bvh, d_tri != nullptr, n, d_required, stack_entries, TR_TRIS_STACK, "triangles", nblocks);
 }
 
 template <int MODE>
 int tq_launch(const tr_bvh* bvh, const float* d_tri, int64_t n, uint8_t* out8, int32_t* out32, const int32_t* d_count,
               const int64_t* d_offsets, int64_t total, int32_t* d_face, int stack_entries, int64_t nblocks, void* stream) {
-    hipLaunchKernelGGL(k_tris<MODE>, dim3((unsigned)nblocks), dim3(TQ_BS), 0, (hipStream_t)stream, tq_view(bvh), d_tri, n, out8, out32,
+    hipLaunchKernelGGL(k_tris<MODE>, dim3((unsigned)nblocks), dim3(TQ_BS), 0, (hipStream_t)stream, tr_view_of(bvh), d_tri, n, out8, out32,
                        d_count, d_offsets, total, d_face, stack_entries);
     TR_HIP_TRY(hipGetLastError());
     return TR_OK;
@@ -136,7 +97,7 @@ int tr_tris_any(const tr_bvh* bvh, const float* d_tri, int64_t n, uint8_t* d_any
     if (int rc = tq_check(bvh, d_tri, n, d_any, stack_entries, nblocks)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return tq_launch<TR_TRIS_ANY>(bvh, d_tri, n, d_any, nullptr, nullptr, nullptr, 0, nullptr, stack_entries, nblocks, stream);
 }
 
@@ -145,7 +106,7 @@ int tr_tris_count(const tr_bvh* bvh, const float* d_tri, int64_t n, int32_t* d_c
     if (int rc = tq_check(bvh, d_tri, n, d_count, stack_entries, nblocks)) return rc;
     if (n == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     return tq_launch<TR_TRIS_COUNT>(bvh, d_tri, n, nullptr, d_count, nullptr, nullptr, 0, nullptr, stack_entries, nblocks, stream);
 }
 
@@ -153,12 +114,10 @@ int tr_tris_fill(const tr_bvh* bvh, const float* d_tri, int64_t n, const int32_t
                  int32_t* d_face, int stack_entries, void* stream) {
     int64_t nblocks = 0;
     if (int rc = tq_check(bvh, d_tri, n, d_count, stack_entries, nblocks)) return rc;
-    if (total < 0) return tr_fail(TR_ERR_INVALID_ARG, "total < 0");
-    if (n > 0 && !d_offsets) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument");
-    if (n > 0 && total > 0 && !d_face) return tr_fail(TR_ERR_INVALID_ARG, "null pointer argument (d_face)");
+    TR_TRY(tr_fill_check(n, total, d_offsets, d_face != nullptr, "null pointer argument (d_face)"));
     if (n == 0 || total == 0) return TR_OK;
     tr_device_guard guard;
-    if (guard.enter(bvh->device) != TR_OK) return tr_fail(TR_ERR_NO_DEVICE, "hipSetDevice failed");
+    TR_TRY(tr_enter_device(&guard, bvh->device));
     if (int rc = tq_launch<TR_TRIS_FILL>(bvh, d_tri, n, nullptr, nullptr, d_count, d_offsets, total, d_face, stack_entries, nblocks, stream))
         return rc;
     hipLaunchKernelGGL(k_tris_rows, dim3((unsigned)nblocks), dim3(TQ_BS), 0, (hipStream_t)stream, n, d_count, d_offsets, total, d_face);
