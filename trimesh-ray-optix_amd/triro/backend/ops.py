@@ -117,6 +117,16 @@ ABI = {
 }
 
 
+def _bind(path, abi):
+    """the library at `path` with every symbol of the table {symbol: (restype, argtypes)} declared"""
+    lib = C.CDLL(path)
+    for name, (res, args) in abi.items():
+        fn = getattr(lib, name)   # AttributeError if the library lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def get_module():
     """Load libtriro_hip.so (the counterpart of ops.py:12-46's JIT build + import)."""
     global _lib, _lib_error
@@ -128,11 +138,7 @@ def get_module():
                       f"(or `python -c 'import __graft_entry__ as g; g.build()'`). "
                       f"There is no CPU fallback.")
         raise RuntimeError(_lib_error)
-    lib = C.CDLL(path)
-    for name, (res, args) in ABI.items():
-        fn = getattr(lib, name)   # AttributeError if the library lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    lib = _bind(path, ABI)
     if lib.tr_abi_version() != ABI_VERSION and os.environ.get("TRIRO_ABI_ANY") != "1":      # (TRIRO_ABI_ANY=1: A/B runs against an older build)
         raise RuntimeError(f"libtriro_hip.so ABI version {lib.tr_abi_version()} != {ABI_VERSION} expected by this binding")
     _lib = lib
@@ -174,9 +180,19 @@ def build_sbts():
     """ops.py:77-81 -- no shader binding tables."""
 
 
-# --- marshaling -------------------------------------------------------------------------------
+# --- marshaling: the one path of every query --------------------------------------------------
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _call(fn, device, *args):
+    """Every native call that enqueues work: made on `device`, with torch's current stream of that device as the last
+    argument (each entry of the C ABI takes its stream last), and checked."""
+    if torch.cuda.current_device() == device.index:      # (the usual case; entering a device context costs microseconds)
+        _check(fn(*args, _stream_ptr(device)))
+    else:
+        with torch.cuda.device(device):
+            _check(fn(*args, _stream_ptr(device)))
 
 
 def _fill4(vals, default):
@@ -229,31 +245,75 @@ def _handle(accel_structure, rays_tensor=None):
     return h
 
 
+def _call_rays(fn, handle, origins, dirs, *args):
+    """_call for an entry that takes (handle, rays, ...): on the rays' device"""
+    _call(fn, origins.device, handle, C.byref(make_rays(origins, dirs)), *args)
+
+
 def _new_output(shape, dtype, device) -> torch.Tensor:
     """Every tensor the library writes into -- results and the intermediates count / slots / offsets / total_d -- is born
     here, uninitialised.  One seam, so that a run can swap it to see which bytes no kernel ever wrote (tests/poison.py)."""
     return torch.empty(shape, dtype=dtype, device=device)
 
 
+# the columns of the outputs: (dtype, trailing shape)
+_BOOL, _I32, _I64, _F32 = (torch.bool, ()), (torch.int32, ()), (torch.int64, ()), (torch.float32, ())
+_F32X3, _F32X2 = (torch.float32, (3,)), (torch.float32, (2,))
+
+
+def _outputs(lead, device, *columns):
+    """one new output per column, of shape (*lead, *trailing shape); None for a column that is not wanted (given as False)"""
+    return tuple(_new_output((*lead, *c[1]), c[0], device) if c else None for c in columns)
+
+
+def _ptr(t):
+    """the device pointer of an optional tensor: None if absent"""
+    return t.data_ptr() if t is not None else None
+
+
+def _ptr_rows(t):
+    """the device pointer of an optional output of a fill: None if absent or empty (the fills take NULL for zero rows)"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+_DENSE = (_BOOL, _BOOL, _I32, _F32X3, _F32X2)
+
+
+def _dense_outputs(n, batch, device, outs=None, whose="the rays' device", want_dense=True, want_t=False):
+    """(hit, front, tri, loc, uv, t) of a closest-hit query of n rays: new, of the batch shape, or the caller's `outs`, which
+    must be the five contiguous flat destinations (bool [n], bool [n], int32 [n], float32 [n, 3], float32 [n, 2]) on the
+    query's device.  want_dense=False: hit, front, loc and uv are None; t float32 is new only with want_t."""
+    if outs is not None:
+        if len(outs) != 5 or any(t.dtype != dt or tuple(t.shape) != (n, *tail) or not t.is_contiguous() or t.device != device
+                                 for t, (dt, tail) in zip(outs, _DENSE)):
+            raise ValueError(f"outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on {whose}")
+        return (*outs, None)
+    if batch is None:
+        batch = (n,)
+    hit, front, tri, loc, uv = _DENSE if want_dense else (False, False, _I32, False, False)      # (the triangle index: always)
+    dense = _outputs(batch, device, hit, front, tri, loc, uv, want_t and _F32)
+    if dense[2].numel() != n:
+        raise ValueError(f"batch_shape {tuple(batch)} does not hold {n} rays")
+    return dense
+
+
+def _ray_query(symbol, accel_structure, origins, dirs, column):
+    """a query of libtriro_hip.so with one output per ray"""
+    check_rays(origins, dirs)
+    out, = _outputs(origins.shape[:-1], origins.device, column)
+    _call_rays(getattr(get_module(), symbol), _handle(accel_structure, origins), origins, dirs, out.data_ptr())
+    return out
+
+
 # --- queries (ops.py:84-192) ----------------------------------------------------------------------
 def intersects_any(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:84-100 / ray.cpp:161-189.  Bool[*b]."""
-    check_rays(origins, dirs)
-    out = _new_output(origins.shape[:-1], torch.bool, origins.device)
-    with torch.cuda.device(origins.device):
-        _check(get_module().tr_intersects_any(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                              out.data_ptr(), _stream_ptr(origins.device)))
-    return out
+    return _ray_query("tr_intersects_any", accel_structure, origins, dirs, _BOOL)
 
 
 def intersects_first(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:103-119 / ray.cpp:191-219.  Int32[*b], -1 on miss."""
-    check_rays(origins, dirs)
-    out = _new_output(origins.shape[:-1], torch.int32, origins.device)
-    with torch.cuda.device(origins.device):
-        _check(get_module().tr_intersects_first(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                                out.data_ptr(), _stream_ptr(origins.device)))
-    return out
+    return _ray_query("tr_intersects_first", accel_structure, origins, dirs, _I32)
 
 
 def intersects_closest(accel_structure, origins, dirs, outs=None) -> Tuple[torch.Tensor, ...]:
@@ -261,25 +321,18 @@ def intersects_closest(accel_structure, origins, dirs, outs=None) -> Tuple[torch
     contiguous destinations (bool [n], bool [n], int32 [n], float32 [n, 3], float32 [n, 2] with n = the
     number of rays -- e.g. this rank's rows of gathered full-size outputs, triro.ray.sharded)."""
     check_rays(origins, dirs)
-    b, dev = origins.shape[:-1], origins.device
-    if outs is not None:
-        n = origins.numel() // 3
-        want = ((torch.bool, (n,)), (torch.bool, (n,)), (torch.int32, (n,)), (torch.float32, (n, 3)), (torch.float32, (n, 2)))
-        if len(outs) != 5 or any(t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
-                                 for t, (dt, sh) in zip(outs, want)):
-            raise ValueError("outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on the rays' device")
-        hit, front, tri, loc, uv = outs
-    else:
-        hit = _new_output(b, torch.bool, dev)
-        front = _new_output(b, torch.bool, dev)
-        tri = _new_output(b, torch.int32, dev)
-        loc = _new_output((*b, 3), torch.float32, dev)
-        uv = _new_output((*b, 2), torch.float32, dev)
-    with torch.cuda.device(dev):
-        _check(get_module().tr_intersects_closest(
-            _handle(accel_structure, origins), C.byref(make_rays(origins, dirs)), hit.data_ptr(), front.data_ptr(),
-            tri.data_ptr(), loc.data_ptr(), uv.data_ptr(), _stream_ptr(dev)))
-    return hit, front, tri, loc, uv
+    dense = _dense_outputs(origins.numel() // 3, origins.shape[:-1], origins.device, outs)[:5]
+    _call_rays(get_module().tr_intersects_closest, _handle(accel_structure, origins), origins, dirs, *(t.data_ptr() for t in dense))
+    return dense
+
+
+def _flat_output(out, name, shape, device):
+    """the caller's `out` (`slots`), checked, or a new one: contiguous int32 of shape (n,) or (n, 3) on the rays' device"""
+    if out is None:
+        return _new_output(shape, torch.int32, device)
+    if out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{name} must be a contiguous int32 {'[n]' if len(shape) == 1 else '[n, 3]'} tensor on the rays' device, one row per ray")
+    return out
 
 
 def intersects_closest_packed(accel_structure, origins, dirs, out: torch.Tensor = None, slots: bool = False) -> torch.Tensor:
@@ -288,16 +341,11 @@ def intersects_closest_packed(accel_structure, origins, dirs, out: torch.Tensor 
     dense outputs; `closest_expand` rebuilds those bit for bit.  `out`: optional preallocated [n, 3]
     int32 destination (a slice of a gather buffer)."""
     check_rays(origins, dirs)
-    n, dev = origins.numel() // 3, origins.device
-    if out is None:
-        out = _new_output((n, 3), torch.int32, dev)
-    elif out.dtype != torch.int32 or tuple(out.shape) != (n, 3) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous int32 [n, 3] tensor on the rays' device")
+    out = _flat_output(out, "out", (origins.numel() // 3, 3), origins.device)
     # slots: the record names the ARENA SLOT of the triangle instead of its face index (tr_intersects_closest_packed_slots):
     # cheaper to expand (closest_expand_slots), valid only for this hierarchy or a bit-identical replica of it
     fn = get_module().tr_intersects_closest_packed_slots if slots else get_module().tr_intersects_closest_packed
-    with torch.cuda.device(dev):
-        _check(fn(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)), out.data_ptr(), _stream_ptr(dev)))
+    _call_rays(fn, _handle(accel_structure, origins), origins, dirs, out.data_ptr())
     return out
 
 
@@ -306,14 +354,8 @@ def intersects_closest_slots(accel_structure, origins, dirs, out: torch.Tensor =
     triangle, -1 for a miss.  For a destination that holds the rays (closest_from_slots finishes the query there);
     valid for this hierarchy or a bit-identical replica.  `out`: optional preallocated int32 [n] destination."""
     check_rays(origins, dirs)
-    n, dev = origins.numel() // 3, origins.device
-    if out is None:
-        out = _new_output((n,), torch.int32, dev)
-    elif out.dtype != torch.int32 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous int32 [n] tensor on the rays' device")
-    with torch.cuda.device(dev):
-        _check(get_module().tr_intersects_closest_slots(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                                        out.data_ptr(), _stream_ptr(dev)))
+    out = _flat_output(out, "out", (origins.numel() // 3,), origins.device)
+    _call_rays(get_module().tr_intersects_closest_slots, _handle(accel_structure, origins), origins, dirs, out.data_ptr())
     return out
 
 
@@ -324,26 +366,11 @@ def closest_from_slots(accel_structure, origins, dirs, slots: torch.Tensor, outs
     take the rays' batch shape.  row_length: the rays are whole rows of an image of that width."""
     check_rays(origins, dirs)
     n, dev = origins.numel() // 3, origins.device
-    if slots.dtype != torch.int32 or tuple(slots.shape) != (n,) or not slots.is_contiguous() or slots.device != dev:
-        raise ValueError("slots must be a contiguous int32 [n] tensor on the rays' device, one per ray")
-    if outs is not None:
-        want = ((torch.bool, (n,)), (torch.bool, (n,)), (torch.int32, (n,)), (torch.float32, (n, 3)), (torch.float32, (n, 2)))
-        if len(outs) != 5 or any(t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
-                                 for t, (dt, sh) in zip(outs, want)):
-            raise ValueError("outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on the rays' device")
-        hit, front, tri, loc, uv = outs
-    else:
-        b = origins.shape[:-1]
-        hit = _new_output(b, torch.bool, dev)
-        front = _new_output(b, torch.bool, dev)
-        tri = _new_output(b, torch.int32, dev)
-        loc = _new_output((*b, 3), torch.float32, dev)
-        uv = _new_output((*b, 2), torch.float32, dev)
-    with torch.cuda.device(dev):
-        _check(get_module().tr_closest_from_slots(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                                  slots.data_ptr(), int(row_length), hit.data_ptr(), front.data_ptr(),
-                                                  tri.data_ptr(), loc.data_ptr(), uv.data_ptr(), _stream_ptr(dev)))
-    return hit, front, tri, loc, uv
+    _flat_output(slots, "slots", (n,), dev)
+    dense = _dense_outputs(n, origins.shape[:-1], dev, outs)[:5]
+    _call_rays(get_module().tr_closest_from_slots, _handle(accel_structure, origins), origins, dirs, slots.data_ptr(), int(row_length),
+               *(t.data_ptr() for t in dense))
+    return dense
 
 
 def closest_expand_slots(accel_structure, packed: torch.Tensor, batch_shape=None, outs=None, row_length: int = 0):
@@ -352,27 +379,11 @@ def closest_expand_slots(accel_structure, packed: torch.Tensor, batch_shape=None
     if packed.dtype != torch.int32 or packed.dim() != 2 or packed.shape[1] != 3 or not packed.is_contiguous() or not packed.is_cuda:
         raise ValueError("packed must be a contiguous int32 [n, 3] tensor on the GPU")
     dev, n = packed.device, packed.shape[0]
-    if outs is not None:
-        want = ((torch.bool, (n,)), (torch.bool, (n,)), (torch.int32, (n,)), (torch.float32, (n, 3)), (torch.float32, (n, 2)))
-        if len(outs) != 5 or any(t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
-                                 for t, (dt, sh) in zip(outs, want)):
-            raise ValueError("outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on the device of packed")
-        hit, front, tri, loc, uv = outs
-    else:
-        b = tuple(batch_shape) if batch_shape is not None else (n,)
-        hit = _new_output(b, torch.bool, dev)
-        front = _new_output(b, torch.bool, dev)
-        tri = _new_output(b, torch.int32, dev)
-        loc = _new_output((*b, 3), torch.float32, dev)
-        uv = _new_output((*b, 2), torch.float32, dev)
-        if hit.numel() != n:
-            raise ValueError(f"batch_shape {b} does not hold {n} rays")
+    dense = _dense_outputs(n, batch_shape, dev, outs, "the device of packed")[:5]
     # row_length: the records are whole rows of an image of that width (tr_closest_expand_slots_rows: 8x8 tiles per wave)
-    with torch.cuda.device(dev):
-        _check(get_module().tr_closest_expand_slots_rows(_handle(accel_structure, packed), packed.data_ptr(), n, int(row_length),
-                                                         hit.data_ptr(), front.data_ptr(), tri.data_ptr(), loc.data_ptr(),
-                                                         uv.data_ptr(), _stream_ptr(dev)))
-    return hit, front, tri, loc, uv
+    _call(get_module().tr_closest_expand_slots_rows, dev, _handle(accel_structure, packed), packed.data_ptr(), n, int(row_length),
+          *(t.data_ptr() for t in dense))
+    return dense
 
 
 def closest_expand(packed: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, batch_shape=None, outs=None):
@@ -385,42 +396,30 @@ def closest_expand(packed: torch.Tensor, vertices: torch.Tensor, faces: torch.Te
         raise ValueError("packed must be a contiguous int32 [n, 3] tensor")
     if vertices.dtype != torch.float32 or faces.dtype != torch.int32 or not vertices.is_contiguous() or not faces.is_contiguous():
         raise ValueError("vertices must be contiguous float32 [nv, 3] and faces contiguous int32 [nf, 3]")
-    dev = packed.device
+    dev, n = packed.device, packed.shape[0]
     if not packed.is_cuda or vertices.device != dev or faces.device != dev:
         raise ValueError("packed, vertices and faces must live on the same GPU")
-    n = packed.shape[0]
-    if outs is not None:
-        want = ((torch.bool, (n,)), (torch.bool, (n,)), (torch.int32, (n,)), (torch.float32, (n, 3)), (torch.float32, (n, 2)))
-        if len(outs) != 5 or any(t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
-                                 for t, (dt, sh) in zip(outs, want)):
-            raise ValueError("outs must be contiguous (bool[n], bool[n], int32[n], float32[n,3], float32[n,2]) on the device of packed")
-        with torch.cuda.device(dev):
-            _check(get_module().tr_closest_expand(packed.data_ptr(), n, vertices.data_ptr(), vertices.shape[0],
-                                                  faces.data_ptr(), faces.shape[0], *(t.data_ptr() for t in outs), _stream_ptr(dev)))
-        return tuple(outs)
-    b = tuple(batch_shape) if batch_shape is not None else (n,)
-    hit = _new_output(b, torch.bool, dev)
-    front = _new_output(b, torch.bool, dev)
-    tri = _new_output(b, torch.int32, dev)
-    loc = _new_output((*b, 3), torch.float32, dev)
-    uv = _new_output((*b, 2), torch.float32, dev)
-    if hit.numel() != n:
-        raise ValueError(f"batch_shape {b} does not hold {n} rays")
-    with torch.cuda.device(dev):
-        _check(get_module().tr_closest_expand(packed.data_ptr(), n, vertices.data_ptr(), vertices.shape[0],
-                                              faces.data_ptr(), faces.shape[0], hit.data_ptr(), front.data_ptr(),
-                                              tri.data_ptr(), loc.data_ptr(), uv.data_ptr(), _stream_ptr(dev)))
-    return hit, front, tri, loc, uv
+    dense = _dense_outputs(n, batch_shape, dev, outs, "the device of packed")[:5]
+    _call(get_module().tr_closest_expand, dev, packed.data_ptr(), n, vertices.data_ptr(), vertices.shape[0], faces.data_ptr(), faces.shape[0],
+          *(t.data_ptr() for t in dense))
+    return dense
 
 
 def intersects_count(accel_structure, origins, dirs) -> torch.Tensor:
     """ops.py:152-168 / ray.cpp:291-322.  Int32[*b]."""
-    check_rays(origins, dirs)
-    out = _new_output(origins.shape[:-1], torch.int32, origins.device)
-    with torch.cuda.device(origins.device):
-        _check(get_module().tr_intersects_count(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                                out.data_ptr(), _stream_ptr(origins.device)))
-    return out
+    return _ray_query("tr_intersects_count", accel_structure, origins, dirs, _I32)
+
+
+def _scan_counts(count, cap=0x7fffffff):
+    """(offsets int64[n + 1], total) of a flat int32[n] count, each clamped to `cap`: the exclusive scan that a fill takes
+    as offsets[:n], and one host read of the total to size its outputs (ray.cpp:339 .item<int>()).  The grand total lands
+    in offsets[n] on the device and, after the stream is synchronised, on the host."""
+    n, dev = count.shape[0], count.device
+    offsets = _new_output((n + 1,), torch.int64, dev)
+    total = C.c_int64(0)
+    start = offsets.data_ptr()
+    _call(get_module().tr_hits_scan, dev, count.data_ptr(), n, cap, start, start + 8 * n, C.byref(total))
+    return offsets, int(total.value)
 
 
 def intersects_location(accel_structure, origins, dirs, ray_base: int = 0, fused: bool = True) -> Tuple[torch.Tensor, ...]:
@@ -432,48 +431,23 @@ def intersects_location(accel_structure, origins, dirs, ray_base: int = 0, fused
     the slots.  fused=False: the reference's protocol, count pass -> scan -> second traversal
     (ray.cpp:330, 333-342, 372-374); both give identical results."""
     check_rays(origins, dirs)
-    dev = origins.device
-    lib = get_module()
-    n = origins.numel() // 3
+    dev, n, lib = origins.device, origins.numel() // 3, get_module()
     _check_ray_idx_range(n, ray_base, "intersects_location / intersects_id")
+    handle, rays = _handle(accel_structure, origins), C.byref(make_rays(origins, dirs))
+    count = _new_output((n,), torch.int32, dev)
     if fused:
-        with torch.cuda.device(dev):
-            stream = _stream_ptr(dev)
-            rays = make_rays(origins, dirs)
-            count = _new_output(n, torch.int32, dev)
-            slots = _new_output((n, MAX_ANYHIT_SIZE, 2), torch.int32, dev)   # tr_hit_entry {t_key, slot}
-            _check(lib.tr_intersects_count_topk(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
-                                                count.data_ptr(), slots.data_ptr(), stream))
-            offsets = _new_output(n, torch.int64, dev)
-            total_d = _new_output(1, torch.int64, dev)
-            total = C.c_int64(0)
-            _check(lib.tr_hits_scan(count.data_ptr(), n, MAX_ANYHIT_SIZE, offsets.data_ptr(), total_d.data_ptr(),
-                                    C.byref(total), stream))
-            nhits = int(total.value)
-            loc = _new_output((nhits, 3), torch.float32, dev)
-            tri = _new_output(nhits, torch.int32, dev)
-            ray = _new_output(nhits, torch.int32, dev)
-            _check(lib.tr_location_fill_slots(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
-                                              count.data_ptr(), offsets.data_ptr(), slots.data_ptr(),
-                                              loc.data_ptr(), ray.data_ptr(), tri.data_ptr(), ray_base, stream))
-        return loc, ray, tri
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        rays = make_rays(origins, dirs)
-        count = _new_output(n, torch.int32, dev)
-        _check(lib.tr_intersects_count(_handle(accel_structure, origins), C.byref(rays), count.data_ptr(), stream))
-        offsets = _new_output(n, torch.int64, dev)
-        total_d = _new_output(1, torch.int64, dev)
-        total = C.c_int64(0)
-        _check(lib.tr_hits_scan(count.data_ptr(), n, MAX_ANYHIT_SIZE, offsets.data_ptr(), total_d.data_ptr(),
-                                C.byref(total), stream))   # host sync == ray.cpp:339 .item<int>()
-        nhits = int(total.value)
-        loc = _new_output((nhits, 3), torch.float32, dev)
-        tri = _new_output(nhits, torch.int32, dev)
-        ray = _new_output(nhits, torch.int32, dev)
-        _check(lib.tr_intersects_location_fill(_handle(accel_structure, origins), C.byref(rays), MAX_ANYHIT_SIZE,
-                                               offsets.data_ptr(), loc.data_ptr(), ray.data_ptr(),
-                                               tri.data_ptr(), ray_base, stream))
+        slots = _new_output((n, MAX_ANYHIT_SIZE, 2), torch.int32, dev)   # tr_hit_entry {t_key, slot}
+        _call(lib.tr_intersects_count_topk, dev, handle, rays, MAX_ANYHIT_SIZE, count.data_ptr(), slots.data_ptr())
+    else:
+        _call(lib.tr_intersects_count, dev, handle, rays, count.data_ptr())
+    offsets, nhits = _scan_counts(count, MAX_ANYHIT_SIZE)
+    loc, tri, ray = _outputs((nhits,), dev, _F32X3, _I32, _I32)
+    if fused:
+        _call(lib.tr_location_fill_slots, dev, handle, rays, MAX_ANYHIT_SIZE, count.data_ptr(), offsets.data_ptr(), slots.data_ptr(),
+              loc.data_ptr(), ray.data_ptr(), tri.data_ptr(), ray_base)
+    else:
+        _call(lib.tr_intersects_location_fill, dev, handle, rays, MAX_ANYHIT_SIZE, offsets.data_ptr(), loc.data_ptr(), ray.data_ptr(),
+              tri.data_ptr(), ray_base)
     return loc, ray, tri
 
 
@@ -491,49 +465,41 @@ def compact_closest(hit, front, tri, loc, uv, ray_base: int = 0):
     """Fused stream compaction (ray_optix.py:142-144: five boolean-mask gathers, one host
     sync each) -> one scan + one gather kernel, one host sync for the size.
     Returns (front[h], ray_idx[h], tri[h], loc[h,3], uv[h,2])."""
-    dev = hit.device
-    lib = get_module()
-    n = hit.numel()
+    dev, n, lib = hit.device, hit.numel(), get_module()
     _check_ray_idx_range(n, ray_base, "stream compaction")
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        offsets = _new_output(n, torch.int64, dev)
-        total_d = _new_output(1, torch.int64, dev)
-        total = C.c_int64(0)
-        _check(lib.tr_mask_scan(hit.data_ptr(), n, offsets.data_ptr(), total_d.data_ptr(), C.byref(total), stream))
-        h = int(total.value)
-        front_o = _new_output(h, torch.bool, dev) if front is not None else None
-        ray_o = _new_output(h, torch.int32, dev)
-        tri_o = _new_output(h, torch.int32, dev) if tri is not None else None
-        loc_o = _new_output((h, 3), torch.float32, dev) if loc is not None else None
-        uv_o = _new_output((h, 2), torch.float32, dev) if uv is not None else None
-        p = lambda t: t.data_ptr() if t is not None else None
-        _check(lib.tr_compact_closest(hit.data_ptr(), offsets.data_ptr(), n, p(front), p(tri), p(loc), p(uv),
-                                      ray_base, p(front_o), ray_o.data_ptr(), p(tri_o), p(loc_o), p(uv_o), stream))
-    return front_o, ray_o, tri_o, loc_o, uv_o
-
-
-def trace_stats_closest(accel_structure, origins, dirs) -> dict:
-    """Diagnostic: per-launch traversal counters of the instrumented closest-hit kernel."""
-    check_rays(origins, dirs)
-    st = TrTraceStats()
-    with torch.cuda.device(origins.device):
-        _check(get_module().tr_trace_stats_closest(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                                   C.byref(st), _stream_ptr(origins.device)))
-    return dict(rays=st.rays, node_visits=st.node_visits, tri_tests=st.tri_tests, climb_steps=st.climb_steps)
+    offsets, total_d = _outputs((), dev, (torch.int64, (n,)), (torch.int64, (1,)))
+    total = C.c_int64(0)
+    _call(lib.tr_mask_scan, dev, hit.data_ptr(), n, offsets.data_ptr(), total_d.data_ptr(), C.byref(total))
+    outs = _outputs((int(total.value),), dev, front is not None and _BOOL, _I32, tri is not None and _I32, loc is not None and _F32X3,
+                    uv is not None and _F32X2)
+    _call(lib.tr_compact_closest, dev, hit.data_ptr(), offsets.data_ptr(), n, _ptr(front), _ptr(tri), _ptr(loc), _ptr(uv), ray_base,
+          *(_ptr(t) for t in outs))
+    return outs
 
 
 QUERY_IDS = {"any": 0, "first": 1, "closest": 2, "count": 3, "location": 4}
 
 
-def trace_stats(accel_structure, origins, dirs, query: str = "closest") -> dict:
-    """Diagnostic: traversal counters of the instrumented kernel of any query."""
+def _trace_stats(accel_structure, origins, dirs, query=None) -> dict:
+    """the counters of tr_trace_stats_closest (query None) or of tr_trace_stats_query for the query of that name"""
     check_rays(origins, dirs)
     st = TrTraceStats()
-    with torch.cuda.device(origins.device):
-        _check(get_module().tr_trace_stats_query(_handle(accel_structure, origins), C.byref(make_rays(origins, dirs)),
-                                           QUERY_IDS[query], C.byref(st), _stream_ptr(origins.device)))
+    handle, lib = _handle(accel_structure, origins), get_module()
+    if query is None:
+        _call_rays(lib.tr_trace_stats_closest, handle, origins, dirs, C.byref(st))
+    else:
+        _call_rays(lib.tr_trace_stats_query, handle, origins, dirs, QUERY_IDS[query], C.byref(st))
     return dict(rays=st.rays, node_visits=st.node_visits, tri_tests=st.tri_tests, climb_steps=st.climb_steps)
+
+
+def trace_stats_closest(accel_structure, origins, dirs) -> dict:
+    """Diagnostic: per-launch traversal counters of the instrumented closest-hit kernel."""
+    return _trace_stats(accel_structure, origins, dirs)
+
+
+def trace_stats(accel_structure, origins, dirs, query: str = "closest") -> dict:
+    """Diagnostic: traversal counters of the instrumented kernel of any query."""
+    return _trace_stats(accel_structure, origins, dirs, query)
 
 
 def device_topology(device: int = 0) -> dict:
@@ -569,11 +535,7 @@ class _Satellite:
             path = self.path()
             if not os.path.exists(path):
                 raise RuntimeError(f"{path} not found: build it (make -C trimesh-ray-optix_amd/csrc all, __graft_entry__.build())")
-            lib = C.CDLL(path)
-            for name, (res, args) in self.abi.items():
-                fn = getattr(lib, name)   # AttributeError if the library lacks a declared symbol
-                fn.restype = res
-                fn.argtypes = args
+            lib = _bind(path, self.abi)
             want = globals()[f"{self.key.upper()}_ABI_VERSION"]
             if want is not None:
                 have = getattr(lib, f"tr_{self.key}_abi_version")()
@@ -583,51 +545,61 @@ class _Satellite:
         return self.lib
 
 
-def _ptr(t):
-    """the device pointer of an optional tensor: None if absent"""
-    return t.data_ptr() if t is not None else None
-
-
-def _ptr_rows(t):
-    """the device pointer of an optional output of a fill: None if absent or empty (the fills take NULL for zero rows)"""
-    return t.data_ptr() if t is not None and t.numel() else None
-
-
-def _check_points(points):
+def _points_args(points):
+    """(contiguous points, n, device) of float32 points [n, 3] on a GPU"""
     if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
             points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points must be a float32 GPU tensor of shape [n, 3]")
+    return points.contiguous(), points.shape[0], points.device
 
 
-def _check_pair(name_a, a, name_b, b):
-    """two float32 GPU tensors [n, 3] of one shape on one device (the corners of boxes, the origins and normals of planes)"""
+def _pair_args(accel_structure, name_a, a, name_b, b):
+    """(handle, contiguous a, contiguous b, n, device) of two float32 GPU tensors [n, 3] of one shape on one device (the
+    corners of boxes, the origins and normals of planes)"""
     for name, t in ((name_a, a), (name_b, b)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
             raise ValueError(f"{name} must be a float32 GPU tensor of shape [n, 3]")
     if b.device != a.device or b.shape != a.shape:
         raise ValueError(f"{name_a} {tuple(a.shape)} on {a.device} and {name_b} {tuple(b.shape)} on {b.device} "
                          f"must have one shape and one device")
+    return _handle(accel_structure, a), a.contiguous(), b.contiguous(), a.shape[0], a.device
+
+
+def _dense_f32(t, name, n, device, otherwise, whose):
+    """a per-query float32 argument given as a tensor: dense [n] on the queries' device"""
+    if not t.is_cuda or t.device != device or t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be {otherwise} or a contiguous float32 tensor of {n} elements on the {whose}' device")
+    return t
+
+
+def _range_bound(t, name, n, device):
+    """a bound of the range queries: None (the default) or a dense float32 [n] tensor on the rays' device"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be None or a contiguous float32 tensor of {n} elements on the rays' device")
+    return _dense_f32(t, name, n, device, "None", "rays")
+
+
+def _radius(radius, name, n, device, unused=0.0):
+    """(pointer or None, scalar) of a radius as the entries take it: a dense float32 [n] tensor on the points' device (the
+    scalar is then `unused`), or a number, rounded to float32 (beyond its range: +Inf, as a float32 tensor would hold it)"""
+    if isinstance(radius, torch.Tensor):
+        return _dense_f32(radius, name, n, device, "a number", "points").data_ptr(), unused
+    return None, C.c_float(float(radius)).value
+
+
+def _on_scene_device(t, what, device_index):
+    if t.device.index != device_index:
+        raise ValueError(f"{what} are on {t.device} but the scene lives on cuda:{device_index}; move the {what}")
 
 
 def _any_or_count(query, satellite):
-    """(the dtype of the output, the entry point) of the any / count pair of a library: bool and tr_<key>_any, or int32 and
+    """(the column of the output, the entry point) of the any / count pair of a library: bool and tr_<key>_any, or int32 and
     tr_<key>_count"""
     if query not in ("any", "count"):
         raise ValueError(f"query must be 'any' or 'count', got {query!r}")
-    return (torch.bool if query == "any" else torch.int32), getattr(satellite.load(), f"tr_{satellite.key}_{query}")
-
-
-def _scan_counts(count):
-    """(offsets int64[n + 1], total) of a flat int32[n] count: the exclusive scan that a fill takes as offsets[:n], and one
-    host read of the total to size its outputs (as intersects_location)."""
-    n, dev = count.shape[0], count.device
-    offsets = _new_output((n + 1,), torch.int64, dev)
-    total = C.c_int64(0)
-    with torch.cuda.device(dev):
-        # the grand total lands in offsets[n] on the device and, after the stream is synchronised, on the host
-        _check(get_module().tr_hits_scan(count.data_ptr(), n, 0x7fffffff, offsets.data_ptr(), offsets[n:].data_ptr(),
-                                         C.byref(total), _stream_ptr(dev)))
-    return offsets, int(total.value)
+    return (_BOOL if query == "any" else _I32), getattr(satellite.load(), f"tr_{satellite.key}_{query}")
 
 
 def _check_fill(count, offsets, total, n, dev, whose) -> int:
@@ -640,6 +612,16 @@ def _check_fill(count, offsets, total, n, dev, whose) -> int:
     if total < 0:
         raise ValueError("total must not be negative")
     return total
+
+
+def _count_scan_fill(count_native, fill_native, queries, count_args, fill_args):
+    """The list form of a family: (offsets int64[n + 1], *the outputs of its fill) -- one count launch, one scan, one host
+    read of the total to size the outputs (as intersects_location), one fill.  `queries`: the arguments both entries take
+    first, as the caller gave them; each entry checks them once."""
+    count = count_native(*queries, *count_args).reshape(-1)
+    offsets, total = _scan_counts(count)
+    filled = fill_native(*queries, count, offsets[:-1], total, *fill_args)
+    return (offsets, *filled) if isinstance(filled, tuple) else (offsets, filled)
 
 
 # --- the native N-rank step (include/triro_rccl.h, csrc/gather_rccl.cpp) --------------------------------------------
@@ -714,10 +696,8 @@ def contains_points_native(accel_structure, points, direction, box_lo, box_hi, w
     """tr_contains_points: (inside bool[n], broken bool[n], counts int32[2, n] or None, summary int64[2] = {points in the
     box, broken points}) for float32 points [n, 3] and 3-float device tensors direction / box_lo / box_hi (both boxes None:
     no box test).  Nothing is synchronised: the caller reads `summary` when it needs it."""
-    _check_points(points)
-    dev = points.device
+    points, n, dev = _points_args(points)
     handle = _handle(accel_structure, points)
-    points = points.contiguous()
     small = [direction, box_lo, box_hi]
     if (box_lo is None) != (box_hi is None):
         raise ValueError("box_lo and box_hi must both be given or both be None")
@@ -728,15 +708,11 @@ def contains_points_native(accel_structure, points, direction, box_lo, box_hi, w
             raise ValueError("direction, box_lo and box_hi must be tensors of 3 elements")
         small[k] = t.to(device=dev, dtype=torch.float32).contiguous()
     direction, box_lo, box_hi = small
-    n = points.shape[0]
-    inside = _new_output((n,), torch.bool, dev)
-    broken = _new_output((n,), torch.bool, dev)
-    counts = _new_output((2, n), torch.int32, dev) if want_counts else None
-    summary = _new_output((2,), torch.int64, dev)
-    with torch.cuda.device(dev):
-        _check(get_points_module().tr_contains_points(
-            handle, points.data_ptr(), n, direction.data_ptr(), _ptr(box_lo), _ptr(box_hi),
-            inside.data_ptr(), broken.data_ptr(), _ptr(counts), summary.data_ptr(), None, _stream_ptr(dev)))
+    inside, broken = _outputs((n,), dev, _BOOL, _BOOL)
+    counts, = _outputs((2, n), dev, want_counts and _I32)
+    summary, = _outputs((2,), dev, _I64)
+    _call(get_points_module().tr_contains_points, dev, handle, points.data_ptr(), n, direction.data_ptr(), _ptr(box_lo), _ptr(box_hi),
+          inside.data_ptr(), broken.data_ptr(), _ptr(counts), summary.data_ptr(), None)
     return inside, broken, counts, summary
 
 
@@ -760,18 +736,11 @@ def closest_point_native(accel_structure, points, stack_entries=0, want_closest=
     """tr_closest_point: (closest float32[n, 3] or None, distance float32[n] or None, tri int32[n]) for float32 points
     [n, 3] on the handle's GPU.  stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).
     Nothing is allocated by the library and nothing is synchronised."""
-    _check_points(points)
+    points, n, dev = _points_args(points)
     lib = get_nearest_module()
-    dev = points.device
     handle = _handle(accel_structure, points)
-    points = points.contiguous()
-    n = points.shape[0]
-    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
-    distance = _new_output((n,), torch.float32, dev) if want_distance else None
-    tri = _new_output((n,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_closest_point(handle, points.data_ptr(), n, _ptr(closest), _ptr(distance), tri.data_ptr(),
-                                    int(stack_entries), _stream_ptr(dev)))
+    closest, distance, tri = _outputs((n,), dev, want_closest and _F32X3, want_distance and _F32, _I32)
+    _call(lib.tr_closest_point, dev, handle, points.data_ptr(), n, _ptr(closest), _ptr(distance), tri.data_ptr(), int(stack_entries))
     return closest, distance, tri
 
 
@@ -792,14 +761,26 @@ range_library_path = _range.path
 get_range_module = _range.load
 
 
-def _range_bound(t, name, n, dev):
-    """a bound of the range queries: None (the default) or a dense float32 [n] tensor on the rays' device"""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or \
-            tuple(t.shape) != (n,) or not t.is_contiguous():
-        raise ValueError(f"{name} must be None or a contiguous float32 tensor of {n} elements on the rays' device")
-    return t
+def _range_query(fn, handle, origins, dirs, tmin, tmax, column, stack_entries):
+    """an entry (handle, rays, tmin, tmax, out, stack_entries) with one output per ray, for checked rays: on a mesh or on a
+    scene, any or a count of crossings"""
+    dev, n = origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    out, = _outputs(origins.shape[:-1], dev, column)
+    _call_rays(fn, handle, origins, dirs, _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries))
+    return out
+
+
+def _range_closest(fn, handle, with_instance, origins, dirs, tmin, tmax, stack_entries, want_t, want_dense):
+    """an entry (handle, rays, tmin, tmax, [instance,] tri, t, hit, front, loc, uv, stack_entries) for checked rays ->
+    (hit, front, instance or None, tri, loc, uv, t)"""
+    b, dev, n = origins.shape[:-1], origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    inst, = _outputs(b, dev, with_instance and _I32)
+    hit, front, tri, loc, uv, t = _dense_outputs(n, b, dev, want_dense=want_dense, want_t=want_t)
+    _call_rays(fn, handle, origins, dirs, _ptr(tmin), _ptr(tmax), *((inst.data_ptr(),) if with_instance else ()), tri.data_ptr(), _ptr(t),
+               _ptr(hit), _ptr(front), _ptr(loc), _ptr(uv), int(stack_entries))
+    return hit, front, inst, tri, loc, uv, t
 
 
 def range_any_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
@@ -808,15 +789,7 @@ def range_any_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack
     stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).  Nothing is allocated by the
     library and nothing is synchronised."""
     check_rays(origins, dirs)
-    lib = get_range_module()
-    dev, n = origins.device, origins.numel() // 3
-    handle = _handle(accel_structure, origins)
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    out = _new_output(origins.shape[:-1], torch.bool, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_range_any(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
-                                _stream_ptr(dev)))
-    return out
+    return _range_query(get_range_module().tr_range_any, _handle(accel_structure, origins), origins, dirs, tmin, tmax, _BOOL, stack_entries)
 
 
 def range_closest_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0, want_t=True, want_dense=True):
@@ -824,19 +797,8 @@ def range_closest_native(accel_structure, origins, dirs, tmin=None, tmax=None, s
     of the first hit within [tmin, tmax]; a miss is (False, False, -1, 0, 0, +Inf).  want_t=False: t is None;
     want_dense=False: hit, front, loc and uv are None (tri, and t, alone).  Arguments as range_any_native."""
     check_rays(origins, dirs)
-    lib = get_range_module()
-    b, dev, n = origins.shape[:-1], origins.device, origins.numel() // 3
-    handle = _handle(accel_structure, origins)
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    tri = _new_output(b, torch.int32, dev)
-    t = _new_output(b, torch.float32, dev) if want_t else None
-    hit = _new_output(b, torch.bool, dev) if want_dense else None
-    front = _new_output(b, torch.bool, dev) if want_dense else None
-    loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
-    uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_range_closest(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), tri.data_ptr(), _ptr(t), _ptr(hit),
-                                    _ptr(front), _ptr(loc), _ptr(uv), int(stack_entries), _stream_ptr(dev)))
+    hit, front, _, tri, loc, uv, t = _range_closest(get_range_module().tr_range_closest, _handle(accel_structure, origins), False, origins, dirs,
+                                                    tmin, tmax, stack_entries, want_t, want_dense)
     return hit, front, tri, loc, uv, t
 
 
@@ -891,9 +853,8 @@ def scene_commit(handle, member_handles, mesh_of_instance, transforms, device_in
         if not h:
             raise RuntimeError(f"member {k}: its acceleration structure has not been built")
     members = (_vp * max(len(member_handles), 1))(*member_handles)
-    with torch.cuda.device(device_index):
-        _check(get_scene_module().tr_scene_commit(handle, members, len(member_handles), mesh_of.ctypes.data, M.ctypes.data, len(mesh_of),
-                                                  _stream_ptr(torch.device("cuda", device_index))))
+    _call(get_scene_module().tr_scene_commit, torch.device("cuda", device_index), handle, members, len(member_handles), mesh_of.ctypes.data,
+          M.ctypes.data, len(mesh_of))
 
 
 def scene_info(handle) -> dict:
@@ -904,8 +865,7 @@ def scene_info(handle) -> dict:
 
 def _scene_rays(origins, dirs, device_index):
     check_rays(origins, dirs)
-    if origins.device.index != device_index:
-        raise ValueError(f"rays are on {origins.device} but the scene lives on cuda:{device_index}; move the rays")
+    _on_scene_device(origins, "rays", device_index)
 
 
 def scene_any_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
@@ -913,14 +873,7 @@ def scene_any_native(handle, device_index, origins, dirs, tmin=None, tmax=None, 
     range_any_native, with the scene handle and its device in place of the acceleration structure.  Nothing is allocated
     by the library and nothing is synchronised."""
     _scene_rays(origins, dirs, device_index)
-    lib = get_scene_module()
-    dev, n = origins.device, origins.numel() // 3
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    out = _new_output(origins.shape[:-1], torch.bool, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_any(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
-                                _stream_ptr(dev)))
-    return out
+    return _range_query(get_scene_module().tr_scene_any, handle, origins, dirs, tmin, tmax, _BOOL, stack_entries)
 
 
 def scene_closest_native(handle, device_index, origins, dirs, tmin=None, tmax=None, stack_entries=0, want_t=True, want_dense=True):
@@ -928,19 +881,8 @@ def scene_closest_native(handle, device_index, origins, dirs, tmin=None, tmax=No
     uv float32[*b, 2]) of the first hit within [tmin, tmax] over all instances; a miss is (False, False, -1, -1, +Inf, 0, 0).
     want_t=False: t is None; want_dense=False: hit, front, loc and uv are None (instance, tri and t alone)."""
     _scene_rays(origins, dirs, device_index)
-    lib = get_scene_module()
-    b, dev, n = origins.shape[:-1], origins.device, origins.numel() // 3
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    inst = _new_output(b, torch.int32, dev)
-    tri = _new_output(b, torch.int32, dev)
-    t = _new_output(b, torch.float32, dev) if want_t else None
-    hit = _new_output(b, torch.bool, dev) if want_dense else None
-    front = _new_output(b, torch.bool, dev) if want_dense else None
-    loc = _new_output((*b, 3), torch.float32, dev) if want_dense else None
-    uv = _new_output((*b, 2), torch.float32, dev) if want_dense else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_closest(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), inst.data_ptr(), tri.data_ptr(), _ptr(t),
-                                    _ptr(hit), _ptr(front), _ptr(loc), _ptr(uv), int(stack_entries), _stream_ptr(dev)))
+    hit, front, inst, tri, loc, uv, t = _range_closest(get_scene_module().tr_scene_closest, handle, True, origins, dirs, tmin, tmax,
+                                                       stack_entries, want_t, want_dense)
     return hit, front, inst, tri, t, loc, uv
 
 
@@ -965,28 +907,19 @@ get_within_module = _within.load
 
 
 def _within_args(accel_structure, points, radius):
-    """(handle, contiguous points, n, device, radius pointer or None, scalar radius, the radius tensor kept alive)"""
-    _check_points(points)
-    dev, n = points.device, points.shape[0]
-    handle = _handle(accel_structure, points)
-    if isinstance(radius, torch.Tensor):
-        if not radius.is_cuda or radius.device != dev or radius.dtype != torch.float32 or tuple(radius.shape) != (n,) or \
-                not radius.is_contiguous():
-            raise ValueError(f"radius must be a number or a contiguous float32 tensor of {n} elements on the points' device")
-        return handle, points.contiguous(), n, dev, radius.data_ptr(), 0.0, radius
-    r = C.c_float(float(radius)).value      # rounded to float32 (beyond its range: +Inf, as a float32 tensor would hold it)
-    return handle, points.contiguous(), n, dev, None, r, None
+    """(handle, contiguous points, n, device, radius pointer or None, scalar radius)"""
+    points, n, dev = _points_args(points)
+    return (_handle(accel_structure, points), points, n, dev, *_radius(radius, "radius", n, dev))
 
 
 def within_native(accel_structure, points, radius, query="any", stack_entries=0) -> torch.Tensor:
     """tr_within_any (query="any": bool[n]) / tr_within_count (query="count": int32[n]) for float32 points [n, 3] on the
     handle's GPU.  radius: a number, or a dense float32 [n] tensor on that GPU.  stack_entries: 0 = the whole stack,
     1 .. capacity for tests (same results).  Nothing is allocated by the library and nothing is synchronised."""
-    dtype, fn = _any_or_count(query, _within)
-    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
-    out = _new_output((n,), dtype, dev)
-    with torch.cuda.device(dev):
-        _check(fn(handle, points.data_ptr(), n, rptr, r, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    column, fn = _any_or_count(query, _within)
+    handle, points, n, dev, rptr, r = _within_args(accel_structure, points, radius)
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, points.data_ptr(), n, rptr, r, out.data_ptr(), int(stack_entries))
     return out
 
 
@@ -997,41 +930,29 @@ def within_fill_native(accel_structure, points, radius, count, offsets, total, w
     offsets int64[n] its exclusive scan (tr_hits_scan) for the same points and radii; total (a Python int) sizes the
     outputs.  Nothing is allocated by the library and nothing is synchronised."""
     lib = get_within_module()
-    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
+    handle, points, n, dev, rptr, r = _within_args(accel_structure, points, radius)
     total = _check_fill(count, offsets, total, n, dev, "points")
-    face = _new_output((total,), torch.int32, dev)
-    distance = _new_output((total,), torch.float32, dev) if want_distance else None
-    closest = _new_output((total, 3), torch.float32, dev) if want_closest else None
-    slot = _new_output((total,), torch.int32, dev) if (want_distance or want_closest) and total > 0 else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_within_fill(handle, points.data_ptr(), n, rptr, r, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
-                                  _ptr_rows(distance), _ptr_rows(closest), _ptr_rows(slot), int(stack_entries), _stream_ptr(dev)))
+    face, distance, closest, slot = _outputs((total,), dev, _I32, want_distance and _F32, want_closest and _F32X3,
+                                             (want_distance or want_closest) and total > 0 and _I32)
+    _call(lib.tr_within_fill, dev, handle, points.data_ptr(), n, rptr, r, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
+          _ptr_rows(distance), _ptr_rows(closest), _ptr_rows(slot), int(stack_entries))
     return face, distance, closest
 
 
 def faces_within_native(accel_structure, points, radius, want_distance=False, want_closest=False, stack_entries=0):
     """(offsets int64[n + 1], face, distance or None, closest or None): one count launch, one scan, one host read of the
     total to size the outputs (as intersects_location), one fill."""
-    handle, points, n, dev, rptr, r, keep = _within_args(accel_structure, points, radius)
-    radius = keep if keep is not None else r
-    count = within_native(accel_structure, points, radius, "count", stack_entries)
-    offsets, total = _scan_counts(count)
-    face, distance, closest = within_fill_native(accel_structure, points, radius, count, offsets[:n], total,
-                                                 want_distance, want_closest, stack_entries)
-    return offsets, face, distance, closest
+    return _count_scan_fill(within_native, within_fill_native, (accel_structure, points, radius), ("count", stack_entries),
+                            (want_distance, want_closest, stack_entries))
 
 
 def within_closest_native(accel_structure, points, radius, stack_entries=0, want_closest=True, want_distance=True):
     """tr_within_closest: closest_point_native bounded by the radius -- (closest float32[n, 3] or None, distance float32[n]
     or None, tri int32[n]), (NaN, +Inf, -1) where no face is within.  radius as for within_native."""
     lib = get_within_module()
-    handle, points, n, dev, rptr, r, _keep = _within_args(accel_structure, points, radius)
-    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
-    distance = _new_output((n,), torch.float32, dev) if want_distance else None
-    tri = _new_output((n,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_within_closest(handle, points.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), tri.data_ptr(),
-                                     int(stack_entries), _stream_ptr(dev)))
+    handle, points, n, dev, rptr, r = _within_args(accel_structure, points, radius)
+    closest, distance, tri = _outputs((n,), dev, want_closest and _F32X3, want_distance and _F32, _I32)
+    _call(lib.tr_within_closest, dev, handle, points.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), tri.data_ptr(), int(stack_entries))
     return closest, distance, tri
 
 
@@ -1053,21 +974,14 @@ boxes_library_path = _boxes.path
 get_boxes_module = _boxes.load
 
 
-def _boxes_args(accel_structure, lo, hi):
-    """(handle, contiguous lo, contiguous hi, n, device)"""
-    _check_pair("lo", lo, "hi", hi)
-    return _handle(accel_structure, lo), lo.contiguous(), hi.contiguous(), lo.shape[0], lo.device
-
-
 def boxes_native(accel_structure, lo, hi, query="any", stack_entries=0) -> torch.Tensor:
     """tr_boxes_any (query="any": bool[n]) / tr_boxes_count (query="count": int32[n]) for the closed boxes [lo, hi], float32
     [n, 3] each, on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing
     is allocated by the library and nothing is synchronised."""
-    dtype, fn = _any_or_count(query, _boxes)
-    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
-    out = _new_output((n,), dtype, dev)
-    with torch.cuda.device(dev):
-        _check(fn(handle, lo.data_ptr(), hi.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    column, fn = _any_or_count(query, _boxes)
+    handle, lo, hi, n, dev = _pair_args(accel_structure, "lo", lo, "hi", hi)
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, lo.data_ptr(), hi.data_ptr(), n, out.data_ptr(), int(stack_entries))
     return out
 
 
@@ -1077,24 +991,18 @@ def boxes_fill_native(accel_structure, lo, hi, count, offsets, total, want_insid
     (tr_hits_scan) for the same boxes; total (a Python int) sizes the outputs.  Nothing is allocated by the library and
     nothing is synchronised."""
     lib = get_boxes_module()
-    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
+    handle, lo, hi, n, dev = _pair_args(accel_structure, "lo", lo, "hi", hi)
     total = _check_fill(count, offsets, total, n, dev, "boxes")
-    face = _new_output((total,), torch.int32, dev)
-    inside = _new_output((total,), torch.bool, dev) if want_inside else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_boxes_fill(handle, lo.data_ptr(), hi.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
-                                 _ptr_rows(inside), int(stack_entries), _stream_ptr(dev)))
+    face, inside = _outputs((total,), dev, _I32, want_inside and _BOOL)
+    _call(lib.tr_boxes_fill, dev, handle, lo.data_ptr(), hi.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face),
+          _ptr_rows(inside), int(stack_entries))
     return face, inside
 
 
 def faces_in_boxes_native(accel_structure, lo, hi, want_inside=False, stack_entries=0):
     """(offsets int64[n + 1], face, inside or None): one count launch, one scan, one host read of the total to size the
     outputs (as faces_within_native), one fill."""
-    handle, lo, hi, n, dev = _boxes_args(accel_structure, lo, hi)
-    count = boxes_native(accel_structure, lo, hi, "count", stack_entries)
-    offsets, total = _scan_counts(count)
-    face, inside = boxes_fill_native(accel_structure, lo, hi, count, offsets[:n], total, want_inside, stack_entries)
-    return offsets, face, inside
+    return _count_scan_fill(boxes_native, boxes_fill_native, (accel_structure, lo, hi), ("count", stack_entries), (want_inside, stack_entries))
 
 
 # --- the faces that meet each query triangle (include/triro_tris.h, csrc/tris.hip) ----------------------------------------
@@ -1126,11 +1034,10 @@ def tris_native(accel_structure, tri, query="any", stack_entries=0) -> torch.Ten
     """tr_tris_any (query="any": bool[n]) / tr_tris_count (query="count": int32[n]) for the query triangles, float32 [n, 3, 3],
     on the handle's GPU.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated
     by the library and nothing is synchronised."""
-    dtype, fn = _any_or_count(query, _tris)
+    column, fn = _any_or_count(query, _tris)
     handle, tri, n, dev = _tris_args(accel_structure, tri)
-    out = _new_output((n,), dtype, dev)
-    with torch.cuda.device(dev):
-        _check(fn(handle, tri.data_ptr(), n, out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, tri.data_ptr(), n, out.data_ptr(), int(stack_entries))
     return out
 
 
@@ -1141,21 +1048,15 @@ def tris_fill_native(accel_structure, tri, count, offsets, total, stack_entries=
     lib = get_tris_module()
     handle, tri, n, dev = _tris_args(accel_structure, tri)
     total = _check_fill(count, offsets, total, n, dev, "triangles")
-    face = _new_output((total,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_tris_fill(handle, tri.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
-                                _ptr_rows(face), int(stack_entries), _stream_ptr(dev)))
+    face, = _outputs((total,), dev, _I32)
+    _call(lib.tr_tris_fill, dev, handle, tri.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(face), int(stack_entries))
     return face
 
 
 def faces_meeting_triangles_native(accel_structure, tri, stack_entries=0):
     """(offsets int64[n + 1], face int32[h]): one count launch, one scan, one host read of the total to size the output (as
     faces_in_boxes_native), one fill."""
-    handle, tri, n, dev = _tris_args(accel_structure, tri)
-    count = tris_native(accel_structure, tri, "count", stack_entries)
-    offsets, total = _scan_counts(count)
-    face = tris_fill_native(accel_structure, tri, count, offsets[:n], total, stack_entries)
-    return offsets, face
+    return _count_scan_fill(tris_native, tris_fill_native, (accel_structure, tri), ("count", stack_entries), (stack_entries,))
 
 
 # --- the faces that each plane meets or cuts, and the section segments (include/triro_planes.h, csrc/planes.hip) -----------
@@ -1177,23 +1078,15 @@ planes_library_path = _planes.path
 get_planes_module = _planes.load
 
 
-def _planes_args(accel_structure, origins, normals):
-    """(handle, contiguous origins, contiguous normals, n, device)"""
-    _check_pair("origins", origins, "normals", normals)
-    return _handle(accel_structure, origins), origins.contiguous(), normals.contiguous(), origins.shape[0], origins.device
-
-
 def planes_native(accel_structure, origins, normals, query="any", cut=False, frontier_entries=0) -> torch.Tensor:
     """tr_planes_any (query="any": bool[n]) / tr_planes_count (query="count": int32[n]) for the planes (origin, normal), float32
     [n, 3] each, on the handle's GPU.  cut: the faces the plane CUTS (those that own a row of the section) instead of the faces
     it meets.  frontier_entries: 0 = the whole frontier, 1 .. capacity for tests (same results).  Nothing is allocated by the
     library and nothing is synchronised."""
-    dtype, fn = _any_or_count(query, _planes)
-    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
-    out = _new_output((n,), dtype, dev)
-    with torch.cuda.device(dev):
-        _check(fn(handle, origins.data_ptr(), normals.data_ptr(), n, out.data_ptr(), 1 if cut else 0, int(frontier_entries),
-                  _stream_ptr(dev)))
+    column, fn = _any_or_count(query, _planes)
+    handle, origins, normals, n, dev = _pair_args(accel_structure, "origins", origins, "normals", normals)
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, origins.data_ptr(), normals.data_ptr(), n, out.data_ptr(), 1 if cut else 0, int(frontier_entries))
     return out
 
 
@@ -1203,27 +1096,21 @@ def planes_fill_native(accel_structure, origins, normals, count, offsets, total,
     scan (tr_hits_scan) for the same planes; total (a Python int) sizes the outputs.  Segments need cut.  Nothing is allocated
     by the library and nothing is synchronised."""
     lib = get_planes_module()
-    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
+    handle, origins, normals, n, dev = _pair_args(accel_structure, "origins", origins, "normals", normals)
     total = _check_fill(count, offsets, total, n, dev, "planes")
     if want_segments and not cut:
         raise ValueError("segments are those of the cut faces: want_segments needs cut=True")
-    face = _new_output((total,), torch.int32, dev)
-    segments = _new_output((total, 2, 3), torch.float32, dev) if want_segments else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_planes_fill(handle, origins.data_ptr(), normals.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
-                                  _ptr_rows(face), _ptr_rows(segments), 1 if cut else 0, int(frontier_entries), _stream_ptr(dev)))
+    face, segments = _outputs((total,), dev, _I32, want_segments and (torch.float32, (2, 3)))
+    _call(lib.tr_planes_fill, dev, handle, origins.data_ptr(), normals.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total,
+          _ptr_rows(face), _ptr_rows(segments), 1 if cut else 0, int(frontier_entries))
     return face, segments
 
 
 def faces_on_planes_native(accel_structure, origins, normals, cut=False, want_segments=False, frontier_entries=0):
     """(offsets int64[n + 1], face, segments or None): one count launch, one scan, one host read of the total to size the
     outputs (as faces_in_boxes_native), one fill."""
-    handle, origins, normals, n, dev = _planes_args(accel_structure, origins, normals)
-    count = planes_native(accel_structure, origins, normals, "count", cut, frontier_entries)
-    offsets, total = _scan_counts(count)
-    face, segments = planes_fill_native(accel_structure, origins, normals, count, offsets[:n], total, cut, want_segments,
-                                        frontier_entries)
-    return offsets, face, segments
+    return _count_scan_fill(planes_native, planes_fill_native, (accel_structure, origins, normals), ("count", cut, frontier_entries),
+                            (cut, want_segments, frontier_entries))
 
 
 # --- every crossing of a ray on a per-ray interval [tmin, tmax] (include/triro_cross.h, csrc/cross.hip) -------------------
@@ -1243,21 +1130,28 @@ cross_library_path = _cross.path
 get_cross_module = _cross.load
 
 
+def _cross_fill(fn, handle, with_instance, origins, dirs, tmin, tmax, count, offsets, total, want_front, want_loc, want_uv, want_ray,
+                ray_base, stack_entries):
+    """an entry (handle, rays, tmin, tmax, count, offsets, total, [instance,] face, t, front, loc, uv, ray, ray_base, slot,
+    stack_entries) for checked rays -> ([instance,] face, t, front or None, loc or None, uv or None, ray or None)"""
+    dev, n = origins.device, origins.numel() // 3
+    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
+    total = _check_fill(count, offsets, total, n, dev, "rays")
+    rows = _outputs((total,), dev, with_instance and _I32, _I32, _F32, want_front and _BOOL, want_loc and _F32X3, want_uv and _F32X2,
+                    want_ray and _I64, (want_front or want_loc or want_uv) and total > 0 and _I32)
+    rows, slot = rows[0 if with_instance else 1:-1], rows[-1]
+    _call_rays(fn, handle, origins, dirs, _ptr_rows(tmin), _ptr_rows(tmax), count.data_ptr(), offsets.data_ptr(), total,
+               *(_ptr_rows(t) for t in rows), int(ray_base), _ptr_rows(slot), int(stack_entries))
+    return rows
+
+
 def cross_count_native(accel_structure, origins, dirs, tmin=None, tmax=None, stack_entries=0) -> torch.Tensor:
     """tr_cross_count: int32[*b], how many triangles each ray crosses within [tmin, tmax] (closed, measured from the origin
     given, no anchoring), uncapped.  Rays as for intersects_any (any strides); tmin / tmax: None or dense float32 [n], n =
     the number of rays.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated by
     the library and nothing is synchronised."""
     check_rays(origins, dirs)
-    lib = get_cross_module()
-    dev, n = origins.device, origins.numel() // 3
-    handle = _handle(accel_structure, origins)
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    out = _new_output(origins.shape[:-1], torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_cross_count(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
-                                  _stream_ptr(dev)))
-    return out
+    return _range_query(get_cross_module().tr_cross_count, _handle(accel_structure, origins), origins, dirs, tmin, tmax, _I32, stack_entries)
 
 
 def cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets, total, want_front=False, want_loc=False,
@@ -1268,33 +1162,16 @@ def cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets
     (tr_hits_scan) for the same rays and bounds; total (a Python int) sizes the outputs.  Nothing is allocated by the library
     and nothing is synchronised."""
     check_rays(origins, dirs)
-    lib = get_cross_module()
-    dev, n = origins.device, origins.numel() // 3
-    handle = _handle(accel_structure, origins)
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    total = _check_fill(count, offsets, total, n, dev, "rays")
-    face = _new_output((total,), torch.int32, dev)
-    t = _new_output((total,), torch.float32, dev)
-    front = _new_output((total,), torch.bool, dev) if want_front else None
-    loc = _new_output((total, 3), torch.float32, dev) if want_loc else None
-    uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
-    ray = _new_output((total,), torch.int64, dev) if want_ray else None
-    slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_cross_fill(handle, C.byref(make_rays(origins, dirs)), _ptr_rows(tmin), _ptr_rows(tmax), count.data_ptr(),
-                                 offsets.data_ptr(), total, _ptr_rows(face), _ptr_rows(t), _ptr_rows(front), _ptr_rows(loc),
-                                 _ptr_rows(uv), _ptr_rows(ray), int(ray_base), _ptr_rows(slot), int(stack_entries), _stream_ptr(dev)))
-    return face, t, front, loc, uv, ray
+    return _cross_fill(get_cross_module().tr_cross_fill, _handle(accel_structure, origins), False, origins, dirs, tmin, tmax, count, offsets,
+                       total, want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)
 
 
 def cross_all_native(accel_structure, origins, dirs, tmin=None, tmax=None, want_front=False, want_loc=False, want_uv=False,
                      want_ray=False, ray_base: int = 0, stack_entries=0):
     """(offsets int64[n + 1], face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened in order:
     one count launch, one scan, one host read of the total to size the outputs (as faces_within_native), one fill."""
-    count = cross_count_native(accel_structure, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
-    offsets, total = _scan_counts(count)
-    return (offsets,) + cross_fill_native(accel_structure, origins, dirs, tmin, tmax, count, offsets[:-1], total, want_front,
-                                          want_loc, want_uv, want_ray, ray_base, stack_entries)
+    return _count_scan_fill(cross_count_native, cross_fill_native, (accel_structure, origins, dirs, tmin, tmax), (stack_entries,),
+                            (want_front, want_loc, want_uv, want_ray, ray_base, stack_entries))
 
 
 # --- every crossing of a world ray over an instanced scene (include/triro_scene_cross.h, csrc/scene_cross.hip) ------------
@@ -1318,14 +1195,7 @@ def scene_cross_count_native(handle, device_index, origins, dirs, tmin=None, tma
     """tr_scene_cross_count: int32[*b], how many (instance, triangle) pairs each world ray crosses within [tmin, tmax],
     uncapped.  Arguments as scene_any_native.  Nothing is allocated by the library and nothing is synchronised."""
     _scene_rays(origins, dirs, device_index)
-    lib = get_scene_cross_module()
-    dev, n = origins.device, origins.numel() // 3
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    out = _new_output(origins.shape[:-1], torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_cross_count(handle, C.byref(make_rays(origins, dirs)), _ptr(tmin), _ptr(tmax), out.data_ptr(), int(stack_entries),
-                                        _stream_ptr(dev)))
-    return out
+    return _range_query(get_scene_cross_module().tr_scene_cross_count, handle, origins, dirs, tmin, tmax, _I32, stack_entries)
 
 
 def scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets, total, want_front=False, want_loc=False,
@@ -1336,34 +1206,16 @@ def scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, cou
     (flattened) and offsets int64[n] its exclusive scan (tr_hits_scan) for the same rays and bounds; total (a Python int)
     sizes the outputs.  Nothing is allocated by the library and nothing is synchronised."""
     _scene_rays(origins, dirs, device_index)
-    lib = get_scene_cross_module()
-    dev, n = origins.device, origins.numel() // 3
-    tmin, tmax = _range_bound(tmin, "tmin", n, dev), _range_bound(tmax, "tmax", n, dev)
-    total = _check_fill(count, offsets, total, n, dev, "rays")
-    inst = _new_output((total,), torch.int32, dev)
-    face = _new_output((total,), torch.int32, dev)
-    t = _new_output((total,), torch.float32, dev)
-    front = _new_output((total,), torch.bool, dev) if want_front else None
-    loc = _new_output((total, 3), torch.float32, dev) if want_loc else None
-    uv = _new_output((total, 2), torch.float32, dev) if want_uv else None
-    ray = _new_output((total,), torch.int64, dev) if want_ray else None
-    slot = _new_output((total,), torch.int32, dev) if (want_front or want_loc or want_uv) and total > 0 else None
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_cross_fill(handle, C.byref(make_rays(origins, dirs)), _ptr_rows(tmin), _ptr_rows(tmax), count.data_ptr(),
-                                       offsets.data_ptr(), total, _ptr_rows(inst), _ptr_rows(face), _ptr_rows(t), _ptr_rows(front),
-                                       _ptr_rows(loc), _ptr_rows(uv), _ptr_rows(ray), int(ray_base), _ptr_rows(slot), int(stack_entries),
-                                       _stream_ptr(dev)))
-    return inst, face, t, front, loc, uv, ray
+    return _cross_fill(get_scene_cross_module().tr_scene_cross_fill, handle, True, origins, dirs, tmin, tmax, count, offsets, total,
+                       want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)
 
 
 def scene_cross_all_native(handle, device_index, origins, dirs, tmin=None, tmax=None, want_front=False, want_loc=False, want_uv=False,
                            want_ray=False, ray_base: int = 0, stack_entries=0):
     """(offsets int64[n + 1], instance, face, t, front or None, loc or None, uv or None, ray or None) for the rays flattened
     in order: one count launch, one scan, one host read of the total to size the outputs, one fill: as cross_all_native."""
-    count = scene_cross_count_native(handle, device_index, origins, dirs, tmin, tmax, stack_entries).reshape(-1)
-    offsets, total = _scan_counts(count)
-    return (offsets,) + scene_cross_fill_native(handle, device_index, origins, dirs, tmin, tmax, count, offsets[:-1], total,
-                                                want_front, want_loc, want_uv, want_ray, ray_base, stack_entries)
+    return _count_scan_fill(scene_cross_count_native, scene_cross_fill_native, (handle, device_index, origins, dirs, tmin, tmax),
+                            (stack_entries,), (want_front, want_loc, want_uv, want_ray, ray_base, stack_entries))
 
 
 # --- which instances of a scene hold a point (include/triro_scene_points.h, csrc/scene_points.hip) -------------------------
@@ -1386,34 +1238,31 @@ get_scene_points_module = _scene_points.load
 
 def _scene_points_args(points, direction, device_index):
     """(contiguous points, contiguous direction, n, device)"""
-    _check_points(points)
-    if points.device.index != device_index:
-        raise ValueError(f"points are on {points.device} but the scene lives on cuda:{device_index}; move the points")
-    if not isinstance(direction, torch.Tensor) or direction.device != points.device or direction.dtype != torch.float32 or direction.numel() != 3:
+    flat, n, dev = _points_args(points)
+    _on_scene_device(points, "points", device_index)
+    if not isinstance(direction, torch.Tensor) or direction.device != dev or direction.dtype != torch.float32 or direction.numel() != 3:
         raise ValueError("direction must be a float32 tensor of three elements on the points' device")
-    return points.contiguous(), direction.reshape(3).contiguous(), points.shape[0], points.device
+    return flat, direction.reshape(3).contiguous(), n, dev
+
+
+def _scene_points_query(query, handle, device_index, points, direction, stack_entries):
+    column, fn = _any_or_count(query, _scene_points)
+    points, direction, n, dev = _scene_points_args(points, direction, device_index)
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, points.data_ptr(), n, direction.data_ptr(), out.data_ptr(), int(stack_entries))
+    return out
 
 
 def scene_points_any_native(handle, device_index, points, direction, stack_entries=0) -> torch.Tensor:
     """tr_scene_points_any: bool[n], is each of points float32 [n, 3] inside some instance, by the parity of the crossings of
     (p, direction) and (p, -direction) per instance.  stack_entries: 0 = the whole stack, 1 .. capacity for tests (same
     results).  Nothing is allocated by the library and nothing is synchronised."""
-    lib = get_scene_points_module()
-    points, direction, n, dev = _scene_points_args(points, direction, device_index)
-    out = _new_output((n,), torch.bool, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_points_any(handle, points.data_ptr(), n, direction.data_ptr(), out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
-    return out
+    return _scene_points_query("any", handle, device_index, points, direction, stack_entries)
 
 
 def scene_points_count_native(handle, device_index, points, direction, stack_entries=0) -> torch.Tensor:
     """tr_scene_points_count: int32[n], how many instances each point is inside.  Arguments as scene_points_any_native."""
-    lib = get_scene_points_module()
-    points, direction, n, dev = _scene_points_args(points, direction, device_index)
-    out = _new_output((n,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_points_count(handle, points.data_ptr(), n, direction.data_ptr(), out.data_ptr(), int(stack_entries), _stream_ptr(dev)))
-    return out
+    return _scene_points_query("count", handle, device_index, points, direction, stack_entries)
 
 
 def scene_points_fill_native(handle, device_index, points, direction, count, offsets, total, stack_entries=0) -> torch.Tensor:
@@ -1424,20 +1273,17 @@ def scene_points_fill_native(handle, device_index, points, direction, count, off
     lib = get_scene_points_module()
     points, direction, n, dev = _scene_points_args(points, direction, device_index)
     total = _check_fill(count, offsets, total, n, dev, "points")
-    inst = _new_output((total,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_points_fill(handle, points.data_ptr(), n, direction.data_ptr(), count.data_ptr(), offsets.data_ptr(), total,
-                                        _ptr_rows(inst), int(stack_entries), _stream_ptr(dev)))
+    inst, = _outputs((total,), dev, _I32)
+    _call(lib.tr_scene_points_fill, dev, handle, points.data_ptr(), n, direction.data_ptr(), count.data_ptr(), offsets.data_ptr(), total,
+          _ptr_rows(inst), int(stack_entries))
     return inst
 
 
 def scene_points_list_native(handle, device_index, points, direction, stack_entries=0):
     """(offsets int64[n + 1], instance int32[h]): one count launch, one scan, one host read of the total to size the output
     (as faces_in_boxes_native), one fill."""
-    points, direction, n, dev = _scene_points_args(points, direction, device_index)
-    count = scene_points_count_native(handle, device_index, points, direction, stack_entries)
-    offsets, total = _scan_counts(count)
-    return offsets, scene_points_fill_native(handle, device_index, points, direction, count, offsets[:n], total, stack_entries)
+    return _count_scan_fill(scene_points_count_native, scene_points_fill_native, (handle, device_index, points, direction),
+                            (stack_entries,), (stack_entries,))
 
 
 # --- the nearest placed triangle of a scene (include/triro_scene_nearest.h, csrc/scene_nearest.hip) ------------------------
@@ -1462,25 +1308,11 @@ def scene_closest_point_native(handle, device_index, points, max_distance=None, 
     in the member mesh; (NaN, +Inf, -1, -1) where there is none.  max_distance: None (unbounded), a number, or a dense
     float32 [n] tensor on that GPU.  stack_entries: 0 = the whole far-child stack, 1 .. capacity for tests (same results).
     Nothing is allocated by the library and nothing is synchronised."""
-    _check_points(points)
-    if points.device.index != device_index:
-        raise ValueError(f"points are on {points.device} but the scene lives on cuda:{device_index}; move the points")
+    flat, n, dev = _points_args(points)
+    _on_scene_device(points, "points", device_index)
     lib = get_scene_nearest_module()
-    dev, n = points.device, points.shape[0]
-    points = points.contiguous()
-    rptr, r = None, float("inf")
-    if isinstance(max_distance, torch.Tensor):
-        if not max_distance.is_cuda or max_distance.device != dev or max_distance.dtype != torch.float32 or \
-                tuple(max_distance.shape) != (n,) or not max_distance.is_contiguous():
-            raise ValueError(f"max_distance must be a number or a contiguous float32 tensor of {n} elements on the points' device")
-        rptr = max_distance.data_ptr()
-    elif max_distance is not None:
-        r = C.c_float(float(max_distance)).value      # rounded to float32 (beyond its range: +Inf, as a float32 tensor would hold it)
-    closest = _new_output((n, 3), torch.float32, dev) if want_closest else None
-    distance = _new_output((n,), torch.float32, dev) if want_distance else None
-    inst = _new_output((n,), torch.int32, dev)
-    tri = _new_output((n,), torch.int32, dev)
-    with torch.cuda.device(dev):
-        _check(lib.tr_scene_closest_point(handle, points.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), inst.data_ptr(),
-                                          tri.data_ptr(), int(stack_entries), _stream_ptr(dev)))
+    rptr, r = (None, float("inf")) if max_distance is None else _radius(max_distance, "max_distance", n, dev, float("inf"))
+    closest, distance, inst, tri = _outputs((n,), dev, want_closest and _F32X3, want_distance and _F32, _I32, _I32)
+    _call(lib.tr_scene_closest_point, dev, handle, flat.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), inst.data_ptr(), tri.data_ptr(),
+          int(stack_entries))
     return closest, distance, inst, tri

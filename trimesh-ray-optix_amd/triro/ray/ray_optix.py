@@ -46,6 +46,89 @@ def _to_device_tensor(x, dtype, device=None) -> torch.Tensor:
     return t.to(device=device, dtype=dtype).contiguous()
 
 
+# --- how every query argument becomes what the native entries take (RayMeshIntersector and RaySceneIntersector) -------------
+def _on_device(x, name, device, cpu_ok=False):
+    """The device rule of an argument: a tensor must be on a GPU, and on `device`, the GPU of the acceleration structure;
+    nothing is moved between GPUs behind the caller's back.  cpu_ok: a host tensor is converted like any array."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda and not cpu_ok:
+            raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
+        if x.is_cuda and x.device != device:
+            raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {device}; "
+                             f"move it or build the intersector on that device")
+
+
+def _query_array(x, name, tail, device):
+    """an argument `name` of shape [*b, *tail], a tensor (_on_device) or an array-like -> contiguous float32 on `device`.
+    tail: (3,) for points, corners, origins and normals, (3, 3) for triangles, () where the caller checks the shape"""
+    _on_device(x, name, device)
+    t = _to_device_tensor(x, torch.float32, device)
+    if t.dim() < len(tail) or tuple(t.shape[t.dim() - len(tail):]) != tail:
+        raise ValueError(f"{name} must have shape [*b, {', '.join(map(str, tail))}], got {tuple(t.shape)}")
+    return t
+
+
+def _flat_queries(x, name, tail, device):
+    """_query_array as the native entries take it: (flat float32 [n, *tail], the batch shape)"""
+    t = _query_array(x, name, tail, device)
+    return t.reshape(-1, *tail), t.shape[:t.dim() - len(tail)]
+
+
+def _query_pair(first, second, names, device):
+    """Two arguments [*b, 3] called `names` (lo and hi of boxes, origins and normals of planes), broadcast against each
+    other, as the native box and plane entries take them: (flat float32 first [n, 3], flat float32 second [n, 3], the batch
+    shape)"""
+    a, b = (_query_array(x, name, (3,), device) for name, x in zip(names, (first, second)))
+    try:
+        shape = torch.broadcast_shapes(a.shape, b.shape)
+    except RuntimeError:
+        raise ValueError(f"{names[0]} of shape {tuple(a.shape)} and {names[1]} of shape {tuple(b.shape)} do not broadcast") from None
+    a, b = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in (a, b))
+    return a, b, shape[:-1]
+
+
+def _query_bound(x, name, batch, device, number_ok=False):
+    """a per-query scalar -- a bound of a range, a radius -- as the native entries take it: None as it is; a Python number
+    as a float where the entry takes one (number_ok); anything else, a host tensor included, a dense float32 [n] tensor on
+    `device`, broadcast to the batch shape"""
+    if x is None or (number_ok and isinstance(x, (int, float))):
+        return x if x is None else float(x)
+    _on_device(x, name, device, cpu_ok=True)
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, np.float32))
+    t = t.to(device=device, dtype=torch.float32)
+    try:
+        t = torch.broadcast_to(t, tuple(batch))
+    except RuntimeError:
+        raise ValueError(f"{name} of shape {tuple(t.shape)} does not broadcast to the batch shape {tuple(batch)}") from None
+    return t.contiguous().reshape(-1)
+
+
+def _range_rays(origins, directions, tmin, tmax, device):
+    """(origins, directions, tmin, tmax) as the native range entries take them: float32 rays [*b, 3] on `device` -- a float32
+    tensor as it is, with its strides: the entries read any -- and bounds None or dense float32 [n]"""
+    rays = []
+    for name, x in (("origins", origins), ("directions", directions)):
+        _on_device(x, name, device)
+        rays.append(x if isinstance(x, torch.Tensor) and x.dtype == torch.float32 else _to_device_tensor(x, torch.float32, device))
+    o, d = rays
+    if o.dim() < 1 or o.shape[-1] != 3 or o.shape != d.shape:
+        raise ValueError(f"origins and directions must have the same shape [*b, 3], got {tuple(o.shape)} and {tuple(d.shape)}")
+    return o, d, _query_bound(tmin, "tmin", o.shape[:-1], device), _query_bound(tmax, "tmax", o.shape[:-1], device)
+
+
+def _segment_rays(p0, p1, device):
+    """the segments from p0 to p1 as range rays: (p0, the float32 p1 - p0, the bound 1 of each: the closed interval is [0, 1])"""
+    a, b = _query_array(p0, "p0", (), device), _query_array(p1, "p1", (), device)
+    if a.dim() < 1 or a.shape[-1] != 3 or a.shape != b.shape:
+        raise ValueError(f"p0 and p1 must have the same shape [*b, 3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    return a, b - a, torch.ones(a.numel() // 3, dtype=torch.float32, device=device)
+
+
+def _with_columns(fixed, *optional):
+    """the result tuple of a list query: the fixed columns, then of the (asked for, column) pairs those that were asked for"""
+    return tuple(fixed) + tuple(column for wanted, column in optional if wanted)
+
+
 class RayMeshIntersector:
     """ray_optix.py:18.  Either `mesh=` or `vertices=` and `faces=` must be provided."""
 
@@ -284,36 +367,12 @@ class RayMeshIntersector:
         return contains
 
     # -- proximity (trimesh.proximity; not in the reference) ----------------------------------
-    def _proximity_points(self, points):
-        """points [*b, 3] as the native proximity entries take them: (flat float32 [n, 3] on the acceleration structure's GPU,
-        the batch shape)"""
+    def _points_and_radius(self, points, radius, name="radius"):
+        """(flat float32 points [n, 3], the batch shape, the radius as a float or dense float32 [n]) on the acceleration
+        structure's GPU"""
         dev = self.mesh_vertices.device
-        if isinstance(points, torch.Tensor):
-            if not points.is_cuda:
-                raise ValueError("points must reside on a GPU (cuda/HIP) device")
-            if points.device != dev:
-                raise ValueError(f"points are on {points.device} but the acceleration structure lives on {dev}; "
-                                 f"move the points or build the intersector on that device")
-        p = _to_device_tensor(points, torch.float32, dev)
-        if p.dim() < 1 or p.shape[-1] != 3:
-            raise ValueError(f"points must have shape [*b, 3], got {tuple(p.shape)}")
-        return p.reshape(-1, 3), p.shape[:-1]
-
-    def _proximity_radius(self, radius, b, name="radius"):
-        """a radius as the native entries take it: a Python float, or -- for anything that is not a single number -- a dense
-        float32 [n] tensor on the acceleration structure's GPU, broadcast to the batch shape `b`"""
-        dev = self.mesh_vertices.device
-        if isinstance(radius, (int, float)):
-            return float(radius)
-        if isinstance(radius, torch.Tensor) and radius.is_cuda and radius.device != dev:
-            raise ValueError(f"{name} is on {radius.device} but the acceleration structure lives on {dev}; "
-                             f"move it or build the intersector on that device")
-        r = _to_device_tensor(radius, torch.float32, dev)
-        try:
-            r = torch.broadcast_to(r, tuple(b))
-        except RuntimeError:
-            raise ValueError(f"{name} of shape {tuple(r.shape)} does not broadcast to the batch shape {tuple(b)}") from None
-        return r.reshape(-1).contiguous()
+        flat, b = _flat_queries(points, "points", (3,), dev)
+        return flat, b, _query_bound(radius, name, b, dev, number_ok=True)
 
     def closest_point(self, points, max_distance=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """trimesh.proximity.closest_point: (closest[*b,3] float32, distance[*b] float32, triangle_id[*b] int32) of
@@ -328,79 +387,56 @@ class RayMeshIntersector:
         search is bounded from the first node.  A triangle at exactly max_distance is within; a point without one, and a
         NaN or negative max_distance, answer (NaN, +Inf, -1).  Where the unbounded answer's float64 squared distance
         is <= max_distance^2 the bounded answer is that answer bit for bit."""
-        flat, b = self._proximity_points(points)
-        if max_distance is None:
+        flat, b, r = self._points_and_radius(points, max_distance, "max_distance")
+        if r is None:
             closest, distance, tri = hops.closest_point_native(self.as_wrapper, flat)
         else:
-            closest, distance, tri = hops.within_closest_native(self.as_wrapper, flat, self._proximity_radius(max_distance, b, "max_distance"))
+            closest, distance, tri = hops.within_closest_native(self.as_wrapper, flat, r)
         return closest.reshape(*b, 3), distance.reshape(b), tri.reshape(b)
 
     def within_any(self, points, radius) -> torch.Tensor:
         """bool[*b]: is any triangle within `radius` of each of points [*b, 3] -- one launch of libtriro_within.so
         (tr_within_any), the proximity analogue of intersects_any.  "Within" is float64 squared distance (closest_point's)
         <= radius^2, not strict.  radius: a number or a tensor that broadcasts to the batch shape; NaN or negative: False."""
-        flat, b = self._proximity_points(points)
-        return hops.within_native(self.as_wrapper, flat, self._proximity_radius(radius, b), "any").reshape(b)
+        flat, b, r = self._points_and_radius(points, radius)
+        return hops.within_native(self.as_wrapper, flat, r, "any").reshape(b)
 
     def within_count(self, points, radius) -> torch.Tensor:
         """int32[*b]: how many triangles are within `radius` of each point (tr_within_count); see within_any"""
-        flat, b = self._proximity_points(points)
-        return hops.within_native(self.as_wrapper, flat, self._proximity_radius(radius, b), "count").reshape(b)
+        flat, b, r = self._points_and_radius(points, radius)
+        return hops.within_native(self.as_wrapper, flat, r, "count").reshape(b)
 
     def faces_within(self, points, radius, return_distance=False, return_closest=False):
         """trimesh.proximity.nearby_faces with an exact radius: (offsets int64[n + 1], tri_idx int32[h][, distance float32[h]]
         [, closest float32[h, 3]]) for the points flattened in order -- the triangles within `radius` of point i are
         tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped; distance and closest are closest_point's values for that
         (point, triangle).  One count launch, one scan, one host read of the total to size the outputs, one fill."""
-        flat, b = self._proximity_points(points)
-        offsets, face, distance, closest = hops.faces_within_native(self.as_wrapper, flat, self._proximity_radius(radius, b),
-                                                                    return_distance, return_closest)
-        return (offsets, face) + ((distance,) if return_distance else ()) + ((closest,) if return_closest else ())
+        flat, b, r = self._points_and_radius(points, radius)
+        offsets, face, distance, closest = hops.faces_within_native(self.as_wrapper, flat, r, return_distance, return_closest)
+        return _with_columns((offsets, face), (return_distance, distance), (return_closest, closest))
 
     # -- box queries (libtriro_boxes.so, include/triro_boxes.h; not in the reference) ---------
-    def _query_pair(self, first, second, names):
-        """Two arguments [*b, 3] called `names` (lo and hi of boxes, origins and normals of planes), broadcast against each
-        other, as the native box and plane entries take them: (flat float32 first [n, 3], flat float32 second [n, 3], the batch
-        shape).  Conversion and device rules are those of _proximity_points, for each of the two."""
-        dev = self.mesh_vertices.device
-        parts = []
-        for name, x in zip(names, (first, second)):
-            if isinstance(x, torch.Tensor):
-                if not x.is_cuda:
-                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
-                if x.device != dev:
-                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
-                                     f"move it or build the intersector on that device")
-            t = _to_device_tensor(x, torch.float32, dev)
-            if t.dim() < 1 or t.shape[-1] != 3:
-                raise ValueError(f"{name} must have shape [*b, 3], got {tuple(t.shape)}")
-            parts.append(t)
-        try:
-            shape = torch.broadcast_shapes(parts[0].shape, parts[1].shape)
-        except RuntimeError:
-            raise ValueError(f"{names[0]} of shape {tuple(parts[0].shape)} and {names[1]} of shape {tuple(parts[1].shape)} "
-                             f"do not broadcast") from None
-        first, second = (torch.broadcast_to(t, shape).reshape(-1, 3).contiguous() for t in parts)
-        return first, second, shape[:-1]
+    def _boxes(self, lo, hi):
+        return _query_pair(lo, hi, ("lo", "hi"), self.mesh_vertices.device)
 
     def boxes_any(self, lo, hi) -> torch.Tensor:
         """bool[*b]: does any triangle meet the closed axis-aligned box [lo, hi] -- one launch of libtriro_boxes.so
         (tr_boxes_any).  lo and hi are [*b, 3] and broadcast against each other.  A triangle MEETS a box when they share a
         point, touching included (csrc/tr_boxes.h has the predicate).  Flat boxes, lines and points are boxes; a box with a NaN,
         an infinity or lo > hi on some axis meets nothing, and a triangle with a non-finite coordinate is never met."""
-        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
+        lo, hi, b = self._boxes(lo, hi)
         return hops.boxes_native(self.as_wrapper, lo, hi, "any").reshape(b)
 
     def boxes_count(self, lo, hi) -> torch.Tensor:
         """int32[*b]: how many triangles meet each box (tr_boxes_count); see boxes_any"""
-        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
+        lo, hi, b = self._boxes(lo, hi)
         return hops.boxes_native(self.as_wrapper, lo, hi, "count").reshape(b)
 
     def faces_in_boxes(self, lo, hi, return_inside=False):
         """(offsets int64[n + 1], tri_idx int32[h][, inside bool[h]]) for the boxes flattened in order -- the triangles that
         meet box i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped; inside[k] says that all three vertices of
         that triangle lie in the box.  One count launch, one scan, one host read of the total to size the outputs, one fill."""
-        lo, hi, b = self._query_pair(lo, hi, ("lo", "hi"))
+        lo, hi, b = self._boxes(lo, hi)
         offsets, face, inside = hops.faces_in_boxes_native(self.as_wrapper, lo, hi, return_inside)
         return (offsets, face) + ((inside,) if return_inside else ())
 
@@ -469,26 +505,29 @@ class RayMeshIntersector:
         return torch.cat(found) if found else empty
 
     # -- plane queries (libtriro_planes.so, include/triro_planes.h; not in the reference) -----
+    def _planes(self, origins, normals):
+        return _query_pair(origins, normals, ("origins", "normals"), self.mesh_vertices.device)
+
     def planes_any(self, origins, normals) -> torch.Tensor:
         """bool[*b]: does any triangle meet the plane through `origins` with the normal `normals` -- one launch of
         libtriro_planes.so (tr_planes_any), one wave per plane.  origins and normals are [*b, 3] and broadcast against each
         other; the normal need not be a unit vector.  A triangle MEETS a plane unless its vertices lie strictly on one side,
         touching included (csrc/tr_planes.h has the predicate).  A plane with a NaN, an infinity or a zero normal meets nothing,
         and a triangle with a non-finite coordinate is never met."""
-        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
+        origins, normals, b = self._planes(origins, normals)
         return hops.planes_native(self.as_wrapper, origins, normals, "any").reshape(b)
 
     def planes_count(self, origins, normals, cut=False) -> torch.Tensor:
         """int32[*b]: how many triangles meet each plane (tr_planes_count), or with cut=True how many it CUTS: the triangles that
         own a segment of the section; see planes_any and section_segments"""
-        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
+        origins, normals, b = self._planes(origins, normals)
         return hops.planes_native(self.as_wrapper, origins, normals, "count", cut).reshape(b)
 
     def faces_on_planes(self, origins, normals, cut=False):
         """(offsets int64[n + 1], tri_idx int32[h]) for the planes flattened in order -- the triangles that meet (cut=True: are
         cut by) plane i are tri_idx[offsets[i]:offsets[i + 1]], ascending, uncapped.  One count launch, one scan, one host read
         of the total to size the outputs, one fill."""
-        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
+        origins, normals, b = self._planes(origins, normals)
         offsets, face, _ = hops.faces_on_planes_native(self.as_wrapper, origins, normals, cut)
         return offsets, face
 
@@ -500,7 +539,7 @@ class RayMeshIntersector:
         the positive side.  A crossing point is interpolated from the negative to the positive end of its edge, so the two
         triangles of an edge agree on it bit for bit and the segments of a closed mesh close into loops exactly.  Launches as
         faces_on_planes."""
-        origins, normals, b = self._query_pair(origins, normals, ("origins", "normals"))
+        origins, normals, b = self._planes(origins, normals)
         return hops.faces_on_planes_native(self.as_wrapper, origins, normals, True, True)
 
     def section_multiplane(self, origin, normal, heights):
@@ -518,19 +557,7 @@ class RayMeshIntersector:
 
     # -- triangle queries (libtriro_tris.so, include/triro_tris.h; not in the reference) ------
     def _query_triangles(self, triangles):
-        """triangles [*b, 3, 3] as the native triangle entries take them: (flat float32 [n, 3, 3], the batch shape).  Conversion
-        and device rules are those of the box queries."""
-        dev = self.mesh_vertices.device
-        if isinstance(triangles, torch.Tensor):
-            if not triangles.is_cuda:
-                raise ValueError("triangles must reside on a GPU (cuda/HIP) device")
-            if triangles.device != dev:
-                raise ValueError(f"triangles is on {triangles.device} but the acceleration structure lives on {dev}; "
-                                 f"move it or build the intersector on that device")
-        t = _to_device_tensor(triangles, torch.float32, dev)
-        if t.dim() < 2 or tuple(t.shape[-2:]) != (3, 3):
-            raise ValueError(f"triangles must have shape [*b, 3, 3], got {tuple(t.shape)}")
-        return t.reshape(-1, 3, 3).contiguous(), t.shape[:-2]
+        return _flat_queries(triangles, "triangles", (3, 3), self.mesh_vertices.device)
 
     def triangles_any(self, triangles) -> torch.Tensor:
         """bool[*b]: does any face of the mesh meet each of triangles [*b, 3, 3] -- one launch of libtriro_tris.so
@@ -560,10 +587,8 @@ class RayMeshIntersector:
         if chunk < 1:
             raise ValueError("chunk must be positive")
         dev = self.mesh_vertices.device
-        for name, x in (("vertices", vertices), ("faces", faces)):
-            if isinstance(x, torch.Tensor) and x.is_cuda and x.device != dev:
-                raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
-                                 f"move it or build the intersector on that device")
+        _on_device(vertices, "vertices", dev, cpu_ok=True)
+        _on_device(faces, "faces", dev, cpu_ok=True)
         v = _to_device_tensor(vertices, torch.float32, dev)
         f = _to_device_tensor(faces, torch.int64, dev)
         if v.dim() != 2 or v.shape[1] != 3:
@@ -602,47 +627,16 @@ class RayMeshIntersector:
         """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
         POSITIVE inside, negative elsewhere (trimesh's convention).  `check_direction` is contains_points' argument."""
         dev = self.mesh_vertices.device
-        if isinstance(points, torch.Tensor) and not points.is_cuda:
-            raise ValueError("points must reside on a GPU (cuda/HIP) device")
-        p = _to_device_tensor(points, torch.float32, dev)
-        if p.dim() < 1 or p.shape[-1] != 3:
-            raise ValueError(f"points must have shape [*b, 3], got {tuple(p.shape)}")
-        b = p.shape[:-1]
-        flat = p.reshape(-1, 3)
+        if isinstance(points, torch.Tensor) and points.is_cuda:
+            points = points.to(dev)         # (the one query that moves a tensor from another GPU: it always has)
+        flat, b = _flat_queries(points, "points", (3,), dev)
         _, distance, _ = hops.closest_point_native(self.as_wrapper, flat, want_closest=False)
         inside = self.contains_points(flat, check_direction)      # (keeps its [n, 3] quirk)
         return torch.where(inside, distance, -distance).reshape(b)
 
     # -- ranges (optixTrace's tmin / tmax; not in the reference, which traces [0, 1e7] always) ------------------------
     def _range_rays(self, origins, directions, tmin, tmax):
-        """(origins, directions, tmin, tmax) as the native range entries take them: float32 rays [*b, 3] on the
-        acceleration structure's GPU, bounds None or dense float32 [n]"""
-        dev = self.mesh_vertices.device
-        for name, x in (("origins", origins), ("directions", directions), ("tmin", tmin), ("tmax", tmax)):
-            if isinstance(x, torch.Tensor):
-                if name in ("origins", "directions") and not x.is_cuda:
-                    raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
-                if x.is_cuda and x.device != dev:
-                    raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
-                                     f"move it or build the intersector on that device")
-        o = origins if isinstance(origins, torch.Tensor) and origins.dtype == torch.float32 else _to_device_tensor(origins, torch.float32, dev)
-        d = directions if isinstance(directions, torch.Tensor) and directions.dtype == torch.float32 else _to_device_tensor(directions, torch.float32, dev)
-        if o.dim() < 1 or o.shape[-1] != 3 or o.shape != d.shape:
-            raise ValueError(f"origins and directions must have the same shape [*b, 3], got {tuple(o.shape)} and {tuple(d.shape)}")
-        b = o.shape[:-1]
-        bounds = []
-        for name, x in (("tmin", tmin), ("tmax", tmax)):
-            if x is None:
-                bounds.append(None)
-                continue
-            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, np.float32))
-            t = t.to(device=dev, dtype=torch.float32)
-            try:
-                t = t.broadcast_to(b)
-            except RuntimeError:
-                raise ValueError(f"{name} of shape {tuple(t.shape)} does not broadcast to the batch shape {tuple(b)}") from None
-            bounds.append(t.contiguous().reshape(-1))
-        return o, d, bounds[0], bounds[1]
+        return _range_rays(origins, directions, tmin, tmax, self.mesh_vertices.device)
 
     def intersects_any_range(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
         """Bool[*b]: is anything hit at a distance t (P = o + t d) with tmin <= t <= tmax, one launch of libtriro_range.so.
@@ -659,33 +653,19 @@ class RayMeshIntersector:
         return hops.range_closest_native(self.as_wrapper, o, d, lo, hi)
 
     def _segment_rays(self, p0, p1):
-        dev = self.mesh_vertices.device
-        for name, x in (("p0", p0), ("p1", p1)):
-            if isinstance(x, torch.Tensor) and not x.is_cuda:
-                raise ValueError(f"{name} must reside on a GPU (cuda/HIP) device")
-            if isinstance(x, torch.Tensor) and x.device != dev:
-                raise ValueError(f"{name} is on {x.device} but the acceleration structure lives on {dev}; "
-                                 f"move it or build the intersector on that device")
-        a, b = _to_device_tensor(p0, torch.float32, dev), _to_device_tensor(p1, torch.float32, dev)
-        if a.dim() < 1 or a.shape[-1] != 3 or a.shape != b.shape:
-            raise ValueError(f"p0 and p1 must have the same shape [*b, 3], got {tuple(a.shape)} and {tuple(b.shape)}")
-        return a, b - a
+        return _segment_rays(p0, p1, self.mesh_vertices.device)
 
     def segments_any(self, p0, p1) -> torch.Tensor:
         """Bool[*b]: is the segment from p0 to p1 blocked.  The ray (p0, the float32 p1 - p0) on the closed interval [0, 1]:
         a surface exactly at either end blocks.  Measured from p0, never anchored."""
-        o, d = self._segment_rays(p0, p1)
-        n = o.numel() // 3
-        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        o, d, one = self._segment_rays(p0, p1)
         return hops.range_any_native(self.as_wrapper, o, d, None, one)
 
     def segments_closest(self, p0, p1):
         """(hit[*b], front[*b], tri_idx[*b], loc[*b,3], uv[*b,2], t[*b]): the first hit of the segment from p0 to p1; t
         is the fraction along it.  The ray (p0, the float32 p1 - p0) on the closed interval [0, 1]: a hit at exactly
         either end counts.  Measured from p0, never anchored."""
-        o, d = self._segment_rays(p0, p1)
-        n = o.numel() // 3
-        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        o, d, one = self._segment_rays(p0, p1)
         return hops.range_closest_native(self.as_wrapper, o, d, None, one)
 
     # -- every crossing within a range (trimesh.ray.intersects_location without a cap; an any-hit program with tmin / tmax) --
@@ -703,26 +683,23 @@ class RayMeshIntersector:
         ordered by (t, triangle index) ascending, uncapped; front, loc and uv are intersects_closest_range's values for that
         (ray, triangle), and the first row of a ray is its answer.  One count launch, one scan, one host read of the total
         to size the outputs, one fill (two launches): the shape of faces_within."""
-        o, d, lo, hi = self._range_rays(origins, directions, tmin, tmax)
+        return self._all(*self._range_rays(origins, directions, tmin, tmax), return_front, return_locations, return_uv)
+
+    def _all(self, o, d, lo, hi, return_front, return_locations, return_uv):
         offsets, face, t, front, loc, uv, _ = hops.cross_all_native(self.as_wrapper, o, d, lo, hi, return_front, return_locations, return_uv)
-        return (offsets, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+        return _with_columns((offsets, face, t), (return_front, front), (return_locations, loc), (return_uv, uv))
 
     def segments_count(self, p0, p1) -> torch.Tensor:
         """int32[*b]: how many triangles the segment from p0 to p1 crosses.  The ray (p0, the float32 p1 - p0) on the closed
         interval [0, 1], as segments_any."""
-        o, d = self._segment_rays(p0, p1)
-        n = o.numel() // 3
-        one = torch.ones(n, dtype=torch.float32, device=o.device)
+        o, d, one = self._segment_rays(p0, p1)
         return hops.cross_count_native(self.as_wrapper, o, d, None, one)
 
     def segments_all(self, p0, p1, return_front=False, return_locations=False, return_uv=False):
         """intersects_all_range for the segments from p0 to p1: the ray (p0, the float32 p1 - p0) on the closed interval
         [0, 1]; t is the fraction along the segment."""
-        o, d = self._segment_rays(p0, p1)
-        n = o.numel() // 3
-        one = torch.ones(n, dtype=torch.float32, device=o.device)
-        offsets, face, t, front, loc, uv, _ = hops.cross_all_native(self.as_wrapper, o, d, None, one, return_front, return_locations, return_uv)
-        return (offsets, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+        o, d, one = self._segment_rays(p0, p1)
+        return self._all(o, d, None, one, return_front, return_locations, return_uv)
 
     # -- extras (not in the reference) -------------------------------------------------------
     def bvh_info(self) -> dict:

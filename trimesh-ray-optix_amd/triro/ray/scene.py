@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 import triro.backend.ops as hops
-from triro.ray.ray_optix import RayMeshIntersector, _default_device
+from triro.ray.ray_optix import (RayMeshIntersector, _default_device, _flat_queries, _query_bound, _range_rays, _segment_rays,
+                                 _with_columns)
 
 
 def _transforms(transforms) -> np.ndarray:
@@ -53,8 +54,6 @@ class RaySceneIntersector:
         if mesh_of.size and (mesh_of.min() < 0 or mesh_of.max() >= len(self.meshes)):
             raise ValueError(f"mesh_of_instance names a mesh outside [0, {len(self.meshes)})")
         self.mesh_of_instance = mesh_of.astype(np.int32)
-        self._helper = RayMeshIntersector.__new__(RayMeshIntersector)      # the ray marshalling of the range methods, which reads the device only
-        self._helper.mesh_vertices = torch.empty((0, 3), dtype=torch.float32, device=self.device)
         self.transforms = np.zeros((0, 12), np.float32)
         self._handle = None
         self._handle = hops.scene_create(self.device.index)
@@ -90,7 +89,7 @@ class RaySceneIntersector:
 
     # -- queries -----------------------------------------------------------------------------
     def _rays(self, origins, directions, tmin, tmax):
-        return self._helper._range_rays(origins, directions, tmin, tmax)
+        return _range_rays(origins, directions, tmin, tmax, self.device)
 
     def intersects_any(self, origins, directions, tmin=None, tmax=None) -> torch.Tensor:
         """Bool[*b]: does the world ray hit any instance at a distance t (P = o + t d) with tmin <= t <= tmax.  The interval
@@ -109,14 +108,12 @@ class RaySceneIntersector:
 
     def segments_any(self, p0, p1) -> torch.Tensor:
         """Bool[*b]: is the segment from p0 to p1 blocked by any instance: the ray (p0, the float32 p1 - p0) on [0, 1]."""
-        o, d = self._helper._segment_rays(p0, p1)
-        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        o, d, one = _segment_rays(p0, p1, self.device)
         return hops.scene_any_native(self._handle, self.device.index, o, d, None, one)
 
     def segments_closest(self, p0, p1):
         """The tuple of intersects_closest for the segment from p0 to p1; t is the fraction along it."""
-        o, d = self._helper._segment_rays(p0, p1)
-        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        o, d, one = _segment_rays(p0, p1, self.device)
         return hops.scene_closest_native(self._handle, self.device.index, o, d, None, one)
 
     # -- every crossing within a range (libtriro_scene_cross.so, include/triro_scene_cross.h) ---------------------------
@@ -129,7 +126,7 @@ class RaySceneIntersector:
     def _all(self, o, d, lo, hi, return_front, return_locations, return_uv):
         offsets, inst, face, t, front, loc, uv, _ = hops.scene_cross_all_native(self._handle, self.device.index, o, d, lo, hi, return_front,
                                                                                return_locations, return_uv)
-        return (offsets, inst, face, t) + ((front,) if return_front else ()) + ((loc,) if return_locations else ()) + ((uv,) if return_uv else ())
+        return _with_columns((offsets, inst, face, t), (return_front, front), (return_locations, loc), (return_uv, uv))
 
     def intersects_all(self, origins, directions, tmin=None, tmax=None, return_front=False, return_locations=False, return_uv=False):
         """(offsets int64[n + 1], instance int32[h], tri_idx int32[h], t float32[h][, front bool[h]][, loc float32[h, 3]]
@@ -145,14 +142,12 @@ class RaySceneIntersector:
     def segments_count(self, p0, p1) -> torch.Tensor:
         """int32[*b]: how many (instance, triangle) pairs the segment from p0 to p1 crosses: the ray (p0, the float32
         p1 - p0) on the closed interval [0, 1], as segments_any."""
-        o, d = self._helper._segment_rays(p0, p1)
-        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        o, d, one = _segment_rays(p0, p1, self.device)
         return hops.scene_cross_count_native(self._handle, self.device.index, o, d, None, one)
 
     def segments_all(self, p0, p1, return_front=False, return_locations=False, return_uv=False):
         """intersects_all for the segments from p0 to p1; t is the fraction along the segment."""
-        o, d = self._helper._segment_rays(p0, p1)
-        one = torch.ones(o.numel() // 3, dtype=torch.float32, device=o.device)
+        o, d, one = _segment_rays(p0, p1, self.device)
         return self._all(o, d, None, one, return_front, return_locations, return_uv)
 
     # -- which instances hold a point (libtriro_scene_points.so, include/triro_scene_points.h) ------------------------------
@@ -160,7 +155,7 @@ class RaySceneIntersector:
         """points [*b, 3] and the direction as the native entries take them: (flat float32 [n, 3] on the scene's GPU, float32
         [3] there, the batch shape).  Conversion and device rules for the points are those of the box queries of
         RayMeshIntersector; check_direction is None (the reference's default direction) or three numbers."""
-        flat, b = self._helper._proximity_points(points)
+        flat, b = _flat_queries(points, "points", (3,), self.device)
         if check_direction is None:
             direction = torch.tensor(RayMeshIntersector._DEFAULT_DIRECTION, dtype=torch.float32, device=self.device)
         else:
@@ -206,8 +201,8 @@ class RaySceneIntersector:
 
         max_distance (a number or a tensor that broadcasts to the batch shape; None: unbounded): the nearest placed triangle
         within that distance or none.  A triangle at exactly max_distance is within; NaN or negative: (NaN, +Inf, -1, -1)."""
-        flat, b = self._helper._proximity_points(points)
-        r = None if max_distance is None else self._helper._proximity_radius(max_distance, b, "max_distance")
+        flat, b = _flat_queries(points, "points", (3,), self.device)
+        r = _query_bound(max_distance, "max_distance", b, self.device, number_ok=True)
         closest, distance, inst, tri = hops.scene_closest_point_native(self._handle, self.device.index, flat, r)
         return closest.reshape(*b, 3), distance.reshape(b), inst.reshape(b), tri.reshape(b)
 
