@@ -146,6 +146,24 @@ int tr_bvh_download(const tr_bvh *bvh, void *h_nodes, void *h_links, void *h_tri
  *    a 16-bit grid, used by the unordered count / location schedule) and its grid
  *    (h_frame6 = base[3], scale[3]; plane q of axis k lies at fma(q, scale[k], base[k])).   */
 int tr_bvh_download_qnodes(const tr_bvh *bvh, void *h_qnodes, float *h_frame6, void *stream);
+/*    test hook: the float top of the grid nodes (tr_bvh_set_float_top): *levels = its levels L (0: the handle has no
+ *    hierarchy and nothing is copied), h_top = 8 tables (octant nx | ny << 1 | nz << 2 of the ray directions' signs) of
+ *    2^L - 1 records of 64 bytes in heap order (root 0, children 2i+1 / 2i+2): per child {entry x, entry y}, {exit x,
+ *    exit y}, {entry z, exit z} as floats, then the two child words of the grid node and two zero words.  Either
+ *    pointer may be NULL.  Derived from the grid nodes on every build, refit and load; not part of the serialised blob. */
+int tr_bvh_download_top(const tr_bvh *bvh, void *h_top, int32_t *levels, void *stream);
+/*    The float top of a handle: stealing closest / first / any launches on the grid nodes walk the top levels of the
+ *    tree, while a wave is at one node, from a per-octant table of the planes as floats that every build, refit and load
+ *    keeps current.  on = 0: launches on this handle are handed no table and walk the top from the grid nodes (same
+ *    visits, same results); on != 0 (the state of a new handle): they are.  A launch captured in a HIP graph keeps what
+ *    it was captured with.                                                                                          */
+int tr_bvh_set_float_top(tr_bvh *bvh, int on);
+/*    test hook: overwrite the twelve planes of heap slot `slot` (0 = the root) in all eight tables with h_planes12 (per
+ *    child {entry x, entry y}, {exit x, exit y}, {entry z, exit z}); the child words stay, so no launch follows an index
+ *    the hierarchy does not have.  Lets a test see that a launch reads the table: planes that no ray can meet at the root
+ *    turn every hit of a wave that walks the table into a miss.  The next build, refit or load writes the table anew.
+ *    Synchronises `stream`.                                                                                        */
+int tr_bvh_poke_top(tr_bvh *bvh, int64_t slot, const float *h_planes12, void *stream);
 
 /* -- queries: replace intersectsAny/First/Closest/Count/Location (ray.cpp:161-378,
  *    binding.cpp:49-58).  Output element i belongs to flat ray index i.

@@ -304,6 +304,11 @@ int tr_bvh_deserialize(const void* h_buffer, int64_t size, void* stream, tr_bvh*
                 hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
                 s = tr_fail(TR_ERR_HIP, "upload of the BVH arena failed");
         }
+        // (the float top is derived data and not in the blob: computed from the blob's grid nodes, which lie where the
+        // arena's do)
+        if (s == TR_OK && h.num_nodes > 0)
+            s = tr_top_upload(bvh, (const char*)h_buffer + sizeof h + ((const char*)bvh->qnodes - (const char*)bvh->arena),
+                              h.num_nodes, (hipStream_t)stream);
         if (s == TR_OK) {
             bvh->num_tris = h.num_tris; bvh->num_nodes = h.num_nodes; bvh->depth = h.depth; bvh->key_mode = h.key_mode;
             for (int k = 0; k < 3; k++) { bvh->aabb_min[k] = h.aabb_min[k]; bvh->aabb_max[k] = h.aabb_max[k]; }
@@ -325,6 +330,7 @@ int tr_bvh_destroy(tr_bvh* bvh) {
             if (bvh->arena && hipFree(bvh->arena) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(arena)");
             if (bvh->refit_temp && hipFree(bvh->refit_temp) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(refit_temp)");
             if (bvh->frame_dev && hipFree(bvh->frame_dev) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(frame_dev)");
+            if (bvh->top && hipFree(bvh->top) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(top)");
             if (bvh->wnodes && hipFree(bvh->wnodes) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(wnodes)");
             if (bvh->wflag && hipFree(bvh->wflag) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(wflag)");
             if (bvh->widx && hipFree(bvh->widx) != hipSuccess) status = tr_fail(TR_ERR_HIP, "hipFree(widx)");
@@ -412,6 +418,38 @@ int tr_bvh_download_qnodes(const tr_bvh* bvh, void* h_qnodes, float* h_frame6, v
     TR_HIP_TRY(hipStreamSynchronize(s));
     if (h_frame6)
         for (int k = 0; k < 3; k++) { h_frame6[k] = bvh->frame.base[k]; h_frame6[3 + k] = bvh->frame.scale[k]; }
+    return TR_OK;
+}
+
+int tr_bvh_download_top(const tr_bvh* bvh, void* h_top, int32_t* levels, void* stream) {
+    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
+    hipStream_t s = (hipStream_t)stream;
+    tr_device_guard g;
+    TR_TRY(tr_enter_device(&g, bvh->device));
+    if (levels) *levels = bvh->top && bvh->num_tris >= 2 ? TR_TOP_LEVELS : 0;
+    if (h_top && bvh->top && bvh->num_tris >= 2)
+        TR_HIP_TRY(hipMemcpyAsync(h_top, bvh->top, sizeof(tr_top_rec) * 8 * (size_t)TR_TOP_SLOTS, hipMemcpyDeviceToHost, s));
+    TR_HIP_TRY(hipStreamSynchronize(s));
+    return TR_OK;
+}
+
+int tr_bvh_poke_top(tr_bvh* bvh, int64_t slot, const float* h_planes12, void* stream) {
+    if (!bvh || !h_planes12) return tr_fail(TR_ERR_INVALID_ARG, "null argument");
+    if (!bvh->top || bvh->num_tris < 2) return tr_fail(TR_ERR_INVALID_ARG, "the handle has no float top");
+    if (slot < 0 || slot >= (int64_t)TR_TOP_SLOTS) return tr_fail(TR_ERR_INVALID_ARG, "slot outside the table");
+    hipStream_t s = (hipStream_t)stream;
+    tr_device_guard g;
+    TR_TRY(tr_enter_device(&g, bvh->device));
+    // the twelve planes of the slot's record in each of the eight tables; the child words behind them stay as they are
+    for (size_t o = 0; o < 8; o++)
+        TR_HIP_TRY(hipMemcpyAsync(bvh->top + o * TR_TOP_SLOTS + (size_t)slot, h_planes12, sizeof(float) * 12, hipMemcpyHostToDevice, s));
+    TR_HIP_TRY(hipStreamSynchronize(s));
+    return TR_OK;
+}
+
+int tr_bvh_set_float_top(tr_bvh* bvh, int on) {
+    if (!bvh) return tr_fail(TR_ERR_INVALID_ARG, "bvh == NULL");
+    bvh->use_top = on != 0;
     return TR_OK;
 }
 

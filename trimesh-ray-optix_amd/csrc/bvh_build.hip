@@ -22,6 +22,7 @@
 // with depth-bounded keys (top 32 Morton bits << 32 | sorted position), which caps the
 // height at 64 -- the traversal trail is a single 64-bit word.
 #include <string.h>
+#include <vector>
 
 #include "tr_internal.h"
 #include "tr_lbvh.h"
@@ -345,6 +346,31 @@ __global__ void k_qframe_box(const float* __restrict__ box, tr_qframe* __restric
     *frame = f;
 }
 
+// The float top (tr_bvh.h: tr_top_rec), by the first TR_TOP_SLOTS threads of the two kernels that write the grid nodes: thread
+// `slot` walks to the node of its heap slot (tr_top_walk over `kids`, the kernel's own children), quantises that node's two
+// child boxes as the kernel does for the node itself -- nothing another thread of the launch writes is read -- and writes
+// the slot's eight records; zeros where a node on the path is a leaf.  pos: k_emit's layout positions (the children as the
+// arena numbers them; a node not laid out yet -- a speculative emit, which is repeated -- counts as absent), NULL: as they are.
+template <typename Kids>
+__device__ void top_slot_emit(tr_top_rec* __restrict__ top, uint32_t slot, Kids kids, const int32_t* __restrict__ pos,
+                              const float* __restrict__ sbox, const float* __restrict__ ibox, const tr_qframe* __restrict__ frame) {
+    int32_t n = tr_top_walk(slot, kids);
+    if (n >= 0 && pos && pos[n] < 0) n = -1;
+    tr_qnode qn;
+    if (n >= 0) {
+        int32_t cl, cr;
+        kids(n, cl, cr);
+        const float* a = cl < 0 ? sbox + 6 * (int64_t)(~cl) : ibox + 6 * (int64_t)cl;
+        const float* b = cr < 0 ? sbox + 6 * (int64_t)(~cr) : ibox + 6 * (int64_t)cr;
+        const tr_qframe f = *frame;
+        tr_qnode_set_box(qn.q, a, a + 3, f);
+        tr_qnode_set_box(qn.q + 3, b, b + 3, f);
+        qn.c0 = (pos && cl >= 0) ? pos[cl] : cl;
+        qn.c1 = (pos && cr >= 0) ? pos[cr] : cr;
+    }
+    tr_top_write_slot(top, n >= 0 ? &qn : nullptr, slot, TR_TOP_SLOTS);
+}
+
 __global__ __launch_bounds__(256) void k_emit(const int32_t* __restrict__ childL,
                                               const int32_t* __restrict__ childR,
                                               const int32_t* __restrict__ parent,
@@ -354,8 +380,11 @@ __global__ __launch_bounds__(256) void k_emit(const int32_t* __restrict__ childL
                                               const int32_t* __restrict__ pos,
                                               tr_node* __restrict__ nodes,
                                               tr_link* __restrict__ links,
-                                              tr_qnode* __restrict__ qnodes) {
+                                              tr_qnode* __restrict__ qnodes,
+                                              tr_top_rec* __restrict__ top) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (top && i < (int64_t)TR_TOP_SLOTS)      // the float top: the walk is over the Karras arrays
+        top_slot_emit(top, (uint32_t)i, [=](int32_t n, int32_t& c0, int32_t& c1) { c0 = childL[n]; c1 = childR[n]; }, pos, sbox, ibox, frame);
     if (i >= ninternal) return;
     int32_t cl = childL[i], cr = childR[i];
     const float* a = cl < 0 ? sbox + 6 * (int64_t)(~cl) : ibox + 6 * (int64_t)cl;
@@ -442,8 +471,11 @@ __global__ __launch_bounds__(256) void k_update_boxes(tr_node* __restrict__ node
                                                       const float* __restrict__ ibox,
                                                       int64_t ninternal,
                                                       const tr_qframe* __restrict__ frame,
-                                                      tr_qnode* __restrict__ qnodes) {
+                                                      tr_qnode* __restrict__ qnodes,
+                                                      tr_top_rec* __restrict__ top) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (top && i < (int64_t)TR_TOP_SLOTS)      // the float top: the walk is over the (unchanged) children of the traversal nodes
+        top_slot_emit(top, (uint32_t)i, [=](int32_t n, int32_t& c0, int32_t& c1) { c0 = nodes[n].c0; c1 = nodes[n].c1; }, nullptr, sbox, ibox, frame);
     if (i >= ninternal) return;
     const int32_t cl = nodes[i].c0, cr = nodes[i].c1;
     const float* a = cl < 0 ? sbox + 6 * (int64_t)(~cl) : ibox + 6 * (int64_t)cl;
@@ -504,6 +536,35 @@ int64_t tr_arena_used_bytes(int64_t nf) { return (int64_t)carve_arena(nullptr, n
 int tr_bvh_sync_frame(tr_bvh* bvh) {
     if (!bvh->frame_dev) TR_HIP_TRY(hipMalloc((void**)&bvh->frame_dev, sizeof(tr_qframe)));
     TR_HIP_TRY(hipMemcpy(bvh->frame_dev, &bvh->frame, sizeof(tr_qframe), hipMemcpyHostToDevice));
+    return TR_OK;
+}
+
+int tr_top_alloc(tr_bvh* bvh) {
+    if (!bvh->top) TR_HIP_TRY(hipMalloc((void**)&bvh->top, sizeof(tr_top_rec) * 8 * (size_t)TR_TOP_SLOTS));
+    return TR_OK;
+}
+
+// the table of an arena that came from a blob: computed on the host from the blob's grid nodes (8 x 4095 records), copied
+// behind the arena on `stream`; the caller synchronises before `h_qnodes` goes away
+int tr_top_upload(tr_bvh* bvh, const void* h_qnodes, int64_t num_nodes, hipStream_t stream) {
+    if (num_nodes < 1) return TR_OK;
+    TR_TRY(tr_top_alloc(bvh));
+    std::vector<tr_top_rec> host((size_t)8 * TR_TOP_SLOTS);
+    // the walk on records copied out one by one: a blob's bytes have no alignment, and its child indices are foreign data
+    // (outside the array: the end of the walk)
+    auto fetch = [&](int32_t node) { tr_qnode q; memcpy(&q, (const char*)h_qnodes + sizeof(tr_qnode) * (size_t)node, sizeof q); return q; };
+    for (uint32_t s = 0; s < TR_TOP_SLOTS; s++) {
+        const int32_t node = tr_top_walk(s, [&](int32_t n, int32_t& c0, int32_t& c1) {
+            const tr_qnode q = fetch(n);
+            c0 = q.c0 < num_nodes ? q.c0 : -1;
+            c1 = q.c1 < num_nodes ? q.c1 : -1;
+        });
+        tr_qnode q;
+        if (node >= 0) q = fetch(node);
+        tr_top_write_slot(host.data(), node >= 0 ? &q : nullptr, s, TR_TOP_SLOTS);
+    }
+    TR_HIP_TRY(hipMemcpyAsync(bvh->top, host.data(), sizeof(tr_top_rec) * host.size(), hipMemcpyHostToDevice, stream));
+    TR_HIP_TRY(hipStreamSynchronize(stream));      // `host` ends here
     return TR_OK;
 }
 
@@ -671,8 +732,10 @@ static int32_t try_hierarchy(tr_bvh* bvh, tr_device_state* st, const build_temps
             hipLaunchKernelGGL(k_layout_round, dim3(gI), dim3(TB), 0, stream, t.cl, t.cr, t.span, t.lpos, t.lbase, t.lflag, ni, lround);
         }
         // harmless if the root is not final yet: it is launched again after the next batch
-        hipLaunchKernelGGL(k_emit, dim3(gI), dim3(TB), 0, stream, t.cl, t.cr, t.par, t.sbox, t.ibox, ni, t.frame,
-                           treelets ? t.lpos : nullptr, bvh->nodes, bvh->links, bvh->qnodes);
+        // (at least TR_TOP_SLOTS threads: the first of them also write the float top)
+        const unsigned gE = (unsigned)cdiv(ni > (int64_t)TR_TOP_SLOTS ? ni : (int64_t)TR_TOP_SLOTS, TB);
+        hipLaunchKernelGGL(k_emit, dim3(gE), dim3(TB), 0, stream, t.cl, t.cr, t.par, t.sbox, t.ibox, ni, t.frame,
+                           treelets ? t.lpos : nullptr, bvh->nodes, bvh->links, bvh->qnodes, bvh->top);
         check(status, hipGetLastError(), "k_emit");
         check(status, hipMemcpyAsync(&root_ready, t.ready, sizeof(int32_t), hipMemcpyDeviceToHost, stream), "memcpy root");
         check(status, hipStreamSynchronize(stream), "sync refit");
@@ -714,6 +777,9 @@ int tr_build_impl(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_
     // From here on there is one exit, which resets the handle on any failure: tr_arena_alloc may have replaced the
     // arena with uninitialised memory, and the handle is about to claim `nf` triangles in it.
     int status = tr_arena_alloc(bvh, nf);
+    // (the float top comes with the handle's first hierarchy and stays where it is: a handle that never has one -- a single
+    // triangle, an empty mesh -- never pays its 2 MiB)
+    if (status == TR_OK && nf >= 2) status = tr_top_alloc(bvh);
     if (status == TR_OK) {
         bvh->num_tris = nf;
         bvh->num_nodes = nf >= 2 ? nf - 1 : 0;
@@ -811,7 +877,8 @@ int tr_refit_impl(tr_bvh* bvh, const float* d_vertices, int64_t nv, const int32_
         for (int32_t round = 1; round <= bvh->depth; round++)
             hipLaunchKernelGGL(k_refit_nodes_round, dim3(gI), dim3(TB), 0, stream, bvh->nodes, t.sbox, t.ibox, t.ready, ni, round);
         hipLaunchKernelGGL(k_qframe_box, dim3(1), dim3(64), 0, stream, t.ibox, d_frame);   // the new root box
-        hipLaunchKernelGGL(k_update_boxes, dim3(gI), dim3(TB), 0, stream, bvh->nodes, t.sbox, t.ibox, ni, d_frame, bvh->qnodes);
+        const unsigned gE = (unsigned)cdiv(ni > (int64_t)TR_TOP_SLOTS ? ni : (int64_t)TR_TOP_SLOTS, TB);   // (its first threads write the float top)
+        hipLaunchKernelGGL(k_update_boxes, dim3(gE), dim3(TB), 0, stream, bvh->nodes, t.sbox, t.ibox, ni, d_frame, bvh->qnodes, bvh->top);
         check(&status, hipGetLastError(), "refit rounds");
     }
     // the new bounds: the root's box, or the box of the single triangle (the box rays are anchored to: also for one triangle)

@@ -186,7 +186,46 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                     const tr_uoctant oct = tr_uniform_octant(sn, sz);
                     int32_t nu = 0;        // the wave's node
                     tr_uwave u;
-                    bool more;             // (one condition of bitwise terms, one branch: the short-circuit form is twenty scalar instructions longer)
+                    bool more = true;      // (one condition of bitwise terms, one branch: the short-circuit form is twenty scalar instructions longer)
+                    // FLOAT TOP: while the wave's node has a slot in the handle's table (tr_bvh.h: tr_top_rec), the trip reads the
+                    // record of (octant, slot) -- one 64-byte line, through the scalar memory path as below -- whose twelve planes
+                    // are floats already and already the entry and exit planes of this octant: the packed fma take them from their
+                    // scalar register pairs, and the selection and the conversions of tr_uniform_test are not run.  Same compares,
+                    // same tr_uniform_wave, same push, same conditions to stop; the slot follows the child the wave goes to
+                    // (2i + 1 / 2i + 2, as a byte offset).  Below the table (`more` still set) the loop behind goes on at `nu`.
+                    if (b.top) {
+                        typedef float tr_rec16 __attribute__((ext_vector_type(16)));      // a record as ONE load of sixteen dwords
+                        typedef const __attribute__((address_space(4))) tr_rec16* tr_crecp;
+                        typedef const __attribute__((address_space(4))) char* tr_cchp;
+                        const tr_cchp tab = (tr_cchp)(unsigned long long)(b.top + tr_octant_index(sn, sz) * TR_TOP_SLOTS);
+                        uint32_t off = 0;      // the slot's byte offset in its table
+                        // (the table's last level as a trip count: the slot is inside the table for TR_TOP_LEVELS trips from the root)
+                        const uint32_t lim = steal_min < trip + TR_TOP_LEVELS ? steal_min : trip + TR_TOP_LEVELS;
+                        int32_t s0, s1;
+                        bool on;               // nothing ends the uniform top
+#pragma unroll 1
+                        do {
+                            const tr_rec16 w = *(tr_crecp)(tab + off);
+                            float p[12];
+#pragma unroll
+                            for (int k = 0; k < 12; k++) p[k] = w[k];
+                            s0 = (int32_t)__float_as_uint(w[12]); s1 = (int32_t)__float_as_uint(w[13]);
+                            bool a0, a1, lt;
+                            tr_top_test<Q>(r, p, res, a0, a1, lt);
+                            if (STATS && go) cnt->nodes++;
+                            u = tr_uniform_wave(act, __builtin_amdgcn_ballot_w64(a0), __builtin_amdgcn_ballot_w64(a1),
+                                                __builtin_amdgcn_ballot_w64(lt), s0, s1);
+                            c0 = s0; c1 = s1;
+                            if (tr_lane_in(u.both, lane)) tr_addr_push(ar, fs.sa, tr_lane_in(u.sw, lane) ? c0 : c1);
+                            TR_CONVERGE();
+                            trip++;
+                            on = ((u.l0 | u.l1 | u.pop) == 0ull) & ((u.sw == 0ull) | (u.sw == act));
+                            off = 2u * off + (u.sw != 0ull ? 128u : 64u);
+                        } while (on & (trip < lim));
+                        more = on & (trip < steal_min);
+                        nu = u.sw != 0ull ? s1 : s0;
+                    }
+                    if (more) {
 #pragma unroll 1
                     do {
                         typedef const __attribute__((address_space(4))) int32_t* tr_ci32p;
@@ -207,6 +246,7 @@ __device__ __forceinline__ bool wave_traverse_steal(const tr_bvh_view& b, tr_ray
                         more = ((u.l0 | u.l1 | u.pop) == 0ull) & ((u.sw == 0ull) | (u.sw == act)) & (trip < steal_min);
                         nu = u.sw != 0ull ? c1 : c0;
                     } while (more);
+                    }
                     l0 = tr_lane_in(u.l0, lane); l1 = tr_lane_in(u.l1, lane);
                     if (go) fs.node = tr_lane_in(u.sw, lane) ? c1 : c0;
                     if (tr_lane_in(u.pop, lane)) fs.node = tr_addr_pop(ar, fs.sa);

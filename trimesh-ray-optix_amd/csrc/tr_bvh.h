@@ -235,6 +235,9 @@ struct tr_bvh_view {
     const tr_qnode* qnodes;   // 32-byte grid nodes of the unordered schedule (same topology as `nodes`)
     tr_qframe frame;
     const tr_qframe* frame_dev;   // device copy of `frame`, kept current by build / refit / load (NULL: host simulation)
+    // the float top (tr_top_rec below): 8 tables of TR_TOP_SLOTS records, kept current by build / refit / load at an address
+    // that never changes.  NULL: none -- an empty handle, a handle with the table switched off (tr_bvh_set_float_top), and every view that is not tr_view_of's
+    const struct tr_top_rec* top = nullptr;
 };
 // first statement of every kernel that takes a view: the frame as it is NOW (a graph replay after a refit: the arguments
 // of the captured launch still hold the old one, and both the grid nodes' decode and the rays' anchor depend on it)
@@ -1200,6 +1203,113 @@ TR_HD bool tr_lane_in(uint64_t mask, int lane) {
 #else
     return ((mask >> lane) & 1ull) != 0ull;
 #endif
+}
+
+// FLOAT TOP: what tr_uniform_test derives from a record and an octant -- which plane of each axis is the entry and which the
+// exit plane, and each chosen 16-bit plane as a float -- depends on the hierarchy alone, and is the same on every trip of
+// every wave of every launch that visits the node from that octant.  It is therefore done once per build and refit, for the
+// top TR_TOP_LEVELS levels of the tree: eight tables, one per octant (index nx | ny << 1 | nz << 2: the axes the rays walk in
+// the negative direction), each an implicit heap -- slot 0 is the root (arena node 0), the children of slot i are 2i + 1 and
+// 2i + 2, a slot exists iff every node on its path is an internal node, absent slots are zero and never read -- of 64-byte
+// records: the twelve planes as floats, in the operand pairs of tr_uniform_test's packed fma, and the children as the grid node
+// holds them.  (float)q is exact for a 16-bit q, so the record's plane has the bits the conversion gives and
+// fma(plane, a, n) is the same number.  Twelve levels: of 8, 10 and 12 the smallest whose table loop runs within 5 % of
+// twelve's trips on the headline (10 levels: 88 %, profiles/r18_float_top_model.txt), and the largest allowed -- 2 MiB, half
+// of one XCD's L2.
+#define TR_TOP_LEVELS 12
+#define TR_TOP_SLOTS ((1u << TR_TOP_LEVELS) - 1u)      // heap slots of one octant's table
+struct alignas(64) tr_top_rec {
+    float p[12];         // per child c: {entry x, entry y}, {exit x, exit y}, {entry z, exit z} at p[6 c ...]
+    int32_t c0, c1;      // the arena indices of the children; negative: a leaf
+    uint32_t pad[2];     // zero
+};
+static_assert(sizeof(tr_top_rec) == 64, "a record of the float top is one 64-byte line");
+TR_HD uint32_t tr_octant_index(uint32_t sel_n, uint32_t sel_z) {
+    return ((sel_n & 0x0400u) ? 1u : 0u) | ((sel_n & 0x04000000u) ? 2u : 0u) | ((sel_z & 2u) ? 4u : 0u);
+}
+// tr_uniform_octant of the rays of octant `o`
+TR_HD tr_uoctant tr_octant_of_index(uint32_t o) {
+    return tr_uoctant{((o & 1u) ? 0xffffu : 0u) | ((o & 2u) ? 0xffff0000u : 0u), (o & 4u) ? 16u : 0u, (o & 4u) ? 0u : 16u};
+}
+// the record of grid node `n` for octant `o`: tr_uniform_test's selection and conversion, statement by statement
+TR_HD void tr_top_fill(tr_top_rec& t, const tr_qnode& n, uint32_t o) {
+    const tr_uoctant oct = tr_octant_of_index(o);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const uint32_t x = (n.q[3 * c] ^ n.q[3 * c + 2]) & oct.mxy;
+        const uint32_t e = n.q[3 * c] ^ x, f = n.q[3 * c + 2] ^ x, z = n.q[3 * c + 1];
+        t.p[6 * c + 0] = (float)(e & 0xffffu); t.p[6 * c + 1] = (float)(e >> 16);
+        t.p[6 * c + 2] = (float)(f & 0xffffu); t.p[6 * c + 3] = (float)(f >> 16);
+        t.p[6 * c + 4] = (float)((z >> oct.she) & 0xffffu); t.p[6 * c + 5] = (float)((z >> oct.shf) & 0xffffu);
+    }
+    t.c0 = n.c0; t.c1 = n.c1;
+    t.pad[0] = 0u; t.pad[1] = 0u;
+}
+// tr_uniform_test on a record of the rays' octant: the same fma per plane, the same tr_slab_hit against the same cull limit,
+// the same three compares.  `p`: the record's twelve planes (on the device: in scalar registers).
+template <int Q, typename P>
+TR_HD void tr_top_test(const tr_ray& r, const P& p, const tr_result& res, bool& a0, bool& a1, bool& lt) {
+    float tn[2], tf[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef float tr_v2 __attribute__((ext_vector_type(2)));
+        const tr_v2 a = __builtin_elementwise_fma(tr_v2{p[6 * c + 0], p[6 * c + 1]}, tr_v2{r.qax, r.qay}, tr_v2{r.qnx, r.qny});
+        const tr_v2 b = __builtin_elementwise_fma(tr_v2{p[6 * c + 2], p[6 * c + 3]}, tr_v2{r.qax, r.qay}, tr_v2{r.qfx, r.qfy});
+        const tr_v2 d = __builtin_elementwise_fma(tr_v2{p[6 * c + 4], p[6 * c + 5]}, tr_v2{r.qaz, r.qaz2}, tr_v2{r.qnz, r.qfz});
+        tn[c] = fmaxf(fmaxf(a.x, a.y), d.x);
+        tf[c] = fminf(fminf(b.x, b.y), d.y);
+#else
+        tn[c] = fmaxf(fmaxf(fmaf(p[6 * c + 0], r.qax, r.qnx), fmaf(p[6 * c + 1], r.qay, r.qny)), fmaf(p[6 * c + 4], r.qaz, r.qnz));
+        tf[c] = fminf(fminf(fmaf(p[6 * c + 2], r.qax, r.qfx), fmaf(p[6 * c + 3], r.qay, r.qfy)), fmaf(p[6 * c + 5], r.qaz, r.qfz));
+#endif
+    }
+    const float lim = tr_cull_limit<Q>(res);
+    a0 = tr_slab_hit(tn[0], tf[0], lim);
+    a1 = tr_slab_hit(tn[1], tf[1], lim);
+    lt = tn[1] < tn[0];
+}
+// The table's builders work slot by slot: the level of heap slot `slot` (the bits of slot + 1 below its leading one are the
+// path from the root: 0 = child 0), and the slot's eight records from its grid node -- `qn` NULL: the slot is absent, zeros.
+// `top`: 8 tables of `slots` records.
+TR_HD int tr_top_level(uint32_t slot) {
+    int level = 0;
+    while (((slot + 1u) >> (level + 1)) != 0u) level++;
+    return level;
+}
+TR_HD void tr_top_write_slot(tr_top_rec* top, const tr_qnode* qn, uint32_t slot, uint32_t slots) {
+    for (uint32_t o = 0; o < 8u; o++) {
+        tr_top_rec t;
+        if (qn) tr_top_fill(t, *qn, o);
+        else { for (int k = 0; k < 12; k++) t.p[k] = 0.f; t.c0 = 0; t.c1 = 0; t.pad[0] = 0u; t.pad[1] = 0u; }
+        top[(size_t)o * slots + slot] = t;
+    }
+}
+// The node of heap slot `slot`: the walk from the root (node 0) along the slot's bits.  kids(node, c0, c1) hands out a
+// node's two children in the caller's numbering; a negative child is a leaf and ends the walk (-> negative: the slot is
+// absent).  ONE walk for the builder's kernels (k_emit over the Karras arrays, k_update_boxes over the traversal nodes), for
+// a load (tr_top_upload, over the blob's bytes on the host) and for tr_top_build_slot.
+template <typename Kids>
+TR_HD int32_t tr_top_walk(uint32_t slot, Kids kids) {
+    const uint32_t path = slot + 1u;
+    int32_t node = 0;
+    for (int k = tr_top_level(slot) - 1; k >= 0 && node >= 0; k--) {
+        int32_t c0, c1;
+        kids(node, c0, c1);
+        node = ((path >> k) & 1u) ? c1 : c0;
+    }
+    return node;
+}
+// The table as a function of the grid nodes alone: what the host simulation and the tests hold the downloaded table to.
+// (The kernels build each record from the boxes they quantise themselves and a load builds it from unaligned bytes, so
+// neither calls this function; they share tr_top_walk, tr_top_fill and tr_top_write_slot with it.)  A child index outside the
+// `num_nodes` grid nodes ends the walk like a leaf.
+TR_HD void tr_top_build_slot(tr_top_rec* top, const tr_qnode* qnodes, int64_t num_nodes, uint32_t slot, uint32_t slots) {
+    const int32_t node = tr_top_walk(slot, [=](int32_t n, int32_t& c0, int32_t& c1) {
+        c0 = qnodes[n].c0 < num_nodes ? qnodes[n].c0 : -1;
+        c1 = qnodes[n].c1 < num_nodes ? qnodes[n].c1 : -1;
+    });
+    tr_top_write_slot(top, node >= 0 ? qnodes + node : nullptr, slot, slots);
 }
 
 

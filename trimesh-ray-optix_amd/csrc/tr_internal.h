@@ -80,6 +80,9 @@ struct tr_bvh {
     tr_qframe frame = {{0, 0, 0}, {1, 1, 1}};   // their grid: a function of the bounds below
     tr_qframe* frame_dev = nullptr;             // ... and its copy in device memory, which the kernels READ (tr_view_live): a launch
                                                 // captured in a HIP graph must see the frame of a later refit, not the one its arguments froze
+    tr_top_rec* top = nullptr;    // the float top of the grid nodes (tr_bvh.h): 8 x TR_TOP_SLOTS records, ONE allocation, made with the handle's first hierarchy and kept for its lifetime
+                                  // (tr_top_alloc) -- a captured launch finds the table of a later refit or rebuild where it found this one
+    bool use_top = true;          // tr_bvh_set_float_top: false = launches on this handle are handed no table
     float aabb_min[3] = {0, 0, 0};
     float aabb_max[3] = {0, 0, 0};
     void* refit_temp = nullptr;   // boxes + flags of tr_bvh_refit, kept between calls (animation loops)
@@ -109,8 +112,15 @@ inline tr_bvh_view tr_view_of(const tr_bvh* bvh) {
     tr_bvh_view view;
     view.nodes = bvh->nodes; view.links = bvh->links; view.tris = bvh->tris; view.num_tris = bvh->num_tris;
     view.qnodes = bvh->qnodes; view.frame = bvh->frame; view.frame_dev = bvh->frame_dev;
+    view.top = bvh->num_tris >= 2 && bvh->use_top ? bvh->top : nullptr;      // (no hierarchy, no table)
     return view;
 }
+
+// the handle's table of the float top, allocated once (with the handle's first hierarchy: build, update or load) and written by k_emit and k_update_boxes beside the
+// grid nodes; tr_top_upload computes it on the host from the grid nodes of a blob and copies it behind the arena, on
+// `stream`, directly behind whatever wrote them (k_emit, k_update_boxes, the upload of a serialised arena)
+int tr_top_alloc(tr_bvh* bvh);
+int tr_top_upload(tr_bvh* bvh, const void* h_qnodes, int64_t num_nodes, hipStream_t stream);
 
 // bvh->frame -> bvh->frame_dev (a small synchronous copy; build / refit / load have just synchronised anyway)
 int tr_bvh_sync_frame(tr_bvh* bvh);

@@ -94,6 +94,9 @@ ABI = {
     "tr_bvh_replica_hash": (_int, [_vp, C.POINTER(C.c_uint64), _vp]),
     "tr_bvh_download": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "tr_bvh_download_qnodes": (_int, [_vp, _vp, _vp, _vp]),
+    "tr_bvh_download_top": (_int, [_vp, _vp, _vp, _vp]),
+    "tr_bvh_set_float_top": (_int, [_vp, _int]),
+    "tr_bvh_poke_top": (_int, [_vp, C.c_int64, _vp, _vp]),
     "tr_intersects_any": (_int, [_vp, C.POINTER(TrRays), _vp, _vp]),
     "tr_intersects_first": (_int, [_vp, C.POINTER(TrRays), _vp, _vp]),
     "tr_intersects_closest": (_int, [_vp, C.POINTER(TrRays), _vp, _vp, _vp, _vp, _vp, _vp]),

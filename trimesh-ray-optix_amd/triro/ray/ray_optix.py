@@ -855,6 +855,31 @@ class OptixAccelStructureWrapper:
             hops._check(hops.get_module().tr_bvh_download_qnodes(self._inner, qn.ctypes.data, frame.ctypes.data, stream))
         return qn, frame
 
+    def set_float_top(self, on: bool):
+        """Hand launches on this handle the table of the float top (the default) or none (tr_bvh_set_float_top)."""
+        hops._check(hops.get_module().tr_bvh_set_float_top(self._inner, int(bool(on))))
+
+    def poke_top(self, slot: int, planes12):
+        """Test hook: overwrite the twelve planes of heap slot `slot` in all eight tables of the float top (tr_bvh_poke_top)."""
+        p = np.ascontiguousarray(planes12, np.float32).reshape(12)
+        with torch.cuda.device(self.info()["device"]):
+            hops._check(hops.get_module().tr_bvh_poke_top(self._inner, int(slot), p.ctypes.data, torch.cuda.current_stream().cuda_stream))
+
+    def download_top(self):
+        """Test hook: the float top of the grid nodes as uint8 (8 octants, 2^levels - 1 slots, 64), or None for a handle
+        without a hierarchy (tr_bvh_download_top)."""
+        inf = self.info()
+        levels = C.c_int32(0)
+        with torch.cuda.device(inf["device"]):
+            stream = torch.cuda.current_stream().cuda_stream
+            lib = hops.get_module()
+            hops._check(lib.tr_bvh_download_top(self._inner, None, C.byref(levels), stream))
+            if levels.value == 0:
+                return None
+            top = np.zeros((8, (1 << levels.value) - 1, 64), np.uint8)
+            hops._check(lib.tr_bvh_download_top(self._inner, top.ctypes.data, None, stream))
+        return top
+
     def download(self):
         """Test hook: (nodes[u32 N,16], links[i32 N,2], tris[u32 F,12]) as numpy arrays."""
         inf = self.info()
