@@ -1062,6 +1062,38 @@ def faces_meeting_triangles_native(accel_structure, tri, stack_entries=0):
     return _count_scan_fill(tris_native, tris_fill_native, (accel_structure, tri), ("count", stack_entries), (stack_entries,))
 
 
+# --- the nearest face to each query triangle (include/triro_tri_nearest.h, csrc/tri_nearest.hip) -------------------------
+TRI_NEAREST_ABI_VERSION = 1    # TR_TRI_NEAREST_ABI_VERSION of include/triro_tri_nearest.h
+
+# every symbol include/triro_tri_nearest.h declares: (restype, argtypes)
+TRI_NEAREST_ABI = {
+    "tr_tri_nearest_abi_version": (_int, []),
+    "tr_tri_nearest_stack_capacity": (_int, []),
+    "tr_triangles_nearest": (_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _int, _vp]),
+}
+
+
+_tri_nearest = _Satellite("tri_nearest", TRI_NEAREST_ABI, get_module)
+tri_nearest_library_path = _tri_nearest.path
+get_tri_nearest_module = _tri_nearest.load
+
+
+def triangles_nearest_native(accel_structure, tri, max_distance=None, stack_entries=0, want=(True, True, True)):
+    """tr_triangles_nearest: (tri int32[n], distance float32[n] or None, closest_mesh float32[n, 3] or None, closest_query
+    float32[n, 3] or None) for the query triangles, float32 [n, 3, 3], on the handle's GPU: the nearest face, its distance and
+    the two nearest points; (-1, +Inf, NaN, NaN) where there is none.  max_distance: None (unbounded), a number, or a dense
+    float32 [n] tensor on that GPU.  want: which of the three optional outputs to produce.  stack_entries: 0 = the whole
+    far-child stack, 1 .. capacity for tests (same results).  Nothing is allocated by the library and nothing is synchronised."""
+    lib = get_tri_nearest_module()
+    handle, tri, n, dev = _tris_args(accel_structure, tri)
+    rptr, r = (None, float("inf")) if max_distance is None else _radius(max_distance, "max_distance", n, dev, float("inf"))
+    want_distance, want_mesh, want_query = want
+    face, distance, on_mesh, on_query = _outputs((n,), dev, _I32, want_distance and _F32, want_mesh and _F32X3, want_query and _F32X3)
+    _call(lib.tr_triangles_nearest, dev, handle, tri.data_ptr(), n, rptr, r, face.data_ptr(), _ptr(distance), _ptr(on_mesh), _ptr(on_query),
+          int(stack_entries))
+    return face, distance, on_mesh, on_query
+
+
 # --- the faces that each plane meets or cuts, and the section segments (include/triro_planes.h, csrc/planes.hip) -----------
 PLANES_ABI_VERSION = 1    # TR_PLANES_ABI_VERSION of include/triro_planes.h
 

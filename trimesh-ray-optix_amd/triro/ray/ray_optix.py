@@ -623,6 +623,53 @@ class RayMeshIntersector:
             found.append(torch.stack((other, own.long()), dim=1))
         return torch.cat(found) if found else torch.zeros((0, 2), dtype=torch.int64, device=dev)
 
+    # -- triangle distances (libtriro_tri_nearest.so, include/triro_tri_nearest.h; not in the reference) ------------------
+    def triangles_nearest(self, triangles, max_distance=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(triangle_id[*b] int32, distance[*b] float32, closest_on_mesh[*b, 3] float32, closest_on_query[*b, 3] float32) of
+        triangles [*b, 3, 3]: the nearest face of the mesh to each query triangle, one launch of libtriro_tri_nearest.so
+        (tr_triangles_nearest).  The squared distance of a pair is evaluated in float64 from the float32 inputs as the minimum
+        over fifteen pairs of points (each vertex against the other triangle, each edge against each edge; csrc/tr_tri_nearest.h
+        has the contract) and is 0 exactly where the two MEET (triangles_any's predicate); among faces at exactly the same
+        distance the smaller face index wins.  The two points are those of the nearest pair; where the triangles meet they are
+        the nearest boundary features, not a common point.  A triangle without area is the segment or point it degenerates to
+        and -- as in triangles_any -- meets nothing, even where it pierces a face.  A query with a NaN or an infinity, an empty
+        mesh or one without an active face: (-1, +Inf, NaN, NaN).
+
+        max_distance (a number or a tensor that broadcasts to the batch shape; None: unbounded): the nearest face within that
+        distance or none.  A face at exactly max_distance is within; NaN or negative: (-1, +Inf, NaN, NaN)."""
+        flat, b = self._query_triangles(triangles)
+        r = _query_bound(max_distance, "max_distance", b, self.mesh_vertices.device, number_ok=True)
+        tri, distance, on_mesh, on_query = hops.triangles_nearest_native(self.as_wrapper, flat, r)
+        return tri.reshape(b), distance.reshape(b), on_mesh.reshape(*b, 3), on_query.reshape(*b, 3)
+
+    def mesh_distance(self, vertices, faces, max_distance=None, chunk=1 << 20):
+        """How far apart are the other mesh (vertices [v, 3], faces [m, 3]) and this one: (distance float32 [], other_face
+        int64 [], face int64 [], point_on_other float32 [3], point_on_self float32 [3]) on the acceleration structure's GPU --
+        the minimum of triangles_nearest over the other mesh's faces, 0 where the meshes collide (mesh_collides' predicate).
+        The winner minimises (float32 distance, other face, this face) lexicographically, `this face` being triangles_nearest's
+        answer for the other face.  No face (an empty mesh on either side, nothing within max_distance, a NaN or negative
+        max_distance): (+Inf, -1, -1, NaN, NaN).
+
+        Host code on triangles_nearest, `chunk` faces of the other mesh per launch, ascending; every chunk after the first is
+        bounded by the best float32 distance r found so far.  That loses nothing and the result does not depend on `chunk`: a
+        pair whose float32 distance is strictly below r has a float64 squared distance <= r * r (r * r is exact in float64, the
+        square root and the rounding to float32 are monotone), so it is within the bound; a pair that rounds to exactly r may
+        be dropped, but it sits in a later chunk and loses the tie against the earlier other face anyway."""
+        tri, chunk = self._other_triangles(vertices, faces, chunk)
+        dev = self.mesh_vertices.device
+        bound = None if max_distance is None else float(max_distance)
+        nan3 = torch.full((3,), float("nan"), dtype=torch.float32, device=dev)
+        best = (torch.tensor(float("inf"), dtype=torch.float32, device=dev), torch.tensor(-1, device=dev), torch.tensor(-1, device=dev), nan3, nan3)
+        for start in range(0, tri.shape[0], chunk):
+            face, distance, on_self, on_other = hops.triangles_nearest_native(self.as_wrapper, tri[start:start + chunk], bound)
+            least = distance.min()
+            if not bool(least < best[0]):      # (strictly: on equal distances the earlier chunk keeps the answer)
+                continue
+            k = torch.nonzero(distance == least)[0, 0]      # the first of equals: the smallest other face
+            best = (least, k + start, face[k].long(), on_other[k], on_self[k])
+            bound = float(least)
+        return best
+
     def signed_distance(self, points, check_direction: Optional[torch.Tensor] = None) -> torch.Tensor:
         """trimesh.proximity.signed_distance: float32[*b], closest_point's distance with the sign of contains_points --
         POSITIVE inside, negative elsewhere (trimesh's convention).  `check_direction` is contains_points' argument."""
