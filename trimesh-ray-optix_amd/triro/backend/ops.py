@@ -1027,10 +1027,11 @@ get_tris_module = _tris.load
 
 
 def _tris_args(accel_structure, tri):
-    """(handle, contiguous triangles, n, device)"""
+    """(handle, contiguous triangles, n, device); accel_structure None (the queries of a scene, whose handle the caller holds):
+    the handle is None"""
     if not isinstance(tri, torch.Tensor) or not tri.is_cuda or tri.dtype != torch.float32 or tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3):
         raise ValueError("triangles must be a float32 GPU tensor of shape [n, 3, 3]")
-    return _handle(accel_structure, tri), tri.contiguous(), tri.shape[0], tri.device
+    return None if accel_structure is None else _handle(accel_structure, tri), tri.contiguous(), tri.shape[0], tri.device
 
 
 def tris_native(accel_structure, tri, query="any", stack_entries=0) -> torch.Tensor:
@@ -1351,3 +1352,61 @@ def scene_closest_point_native(handle, device_index, points, max_distance=None, 
     _call(lib.tr_scene_closest_point, dev, handle, flat.data_ptr(), n, rptr, r, _ptr(closest), _ptr(distance), inst.data_ptr(), tri.data_ptr(),
           int(stack_entries))
     return closest, distance, inst, tri
+
+
+# --- the placed faces of a scene that meet each query triangle (include/triro_scene_tris.h, csrc/scene_tris.hip) -----------
+SCENE_TRIS_ABI_VERSION = 1    # TR_SCENE_TRIS_ABI_VERSION of include/triro_scene_tris.h
+
+# every symbol include/triro_scene_tris.h declares: (restype, argtypes)
+SCENE_TRIS_ABI = {
+    "tr_scene_tris_abi_version": (_int, []),
+    "tr_scene_tris_stack_capacity": (_int, []),
+    "tr_scene_tris_any": (_int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_scene_tris_count": (_int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    "tr_scene_tris_fill": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
+}
+
+
+_scene_tris = _Satellite("scene_tris", SCENE_TRIS_ABI, get_scene_module)   # the scene handles are libtriro_scene.so's
+scene_tris_library_path = _scene_tris.path
+get_scene_tris_module = _scene_tris.load
+
+
+def _scene_tris_args(tri, device_index):
+    """(contiguous triangles, n, device) of float32 triangles [n, 3, 3] on the scene's GPU"""
+    _, flat, n, dev = _tris_args(None, tri)
+    _on_scene_device(tri, "triangles", device_index)
+    return flat, n, dev
+
+
+def scene_tris_native(handle, device_index, tri, query="any", stack_entries=0) -> torch.Tensor:
+    """tr_scene_tris_any (query="any": bool[n]) / tr_scene_tris_count (query="count": int32[n]) for the world triangles, float32
+    [n, 3, 3], on the scene's GPU: does any / how many (instance, face) pairs of the placed copies meet each.  stack_entries:
+    0 = the whole stack, 1 .. capacity for tests (same results).  Nothing is allocated by the library and nothing is
+    synchronised."""
+    column, fn = _any_or_count(query, _scene_tris)
+    tri, n, dev = _scene_tris_args(tri, device_index)
+    out, = _outputs((n,), dev, column)
+    _call(fn, dev, handle, tri.data_ptr(), n, out.data_ptr(), int(stack_entries))
+    return out
+
+
+def scene_tris_fill_native(handle, device_index, tri, count, offsets, total, stack_entries=0):
+    """tr_scene_tris_fill: (instance int32[total], face int32[total]), the pairs of query i ascending by (instance, face index in
+    the member mesh) at rows offsets[i] .. offsets[i] + count[i].  count int32[n] is scene_tris_native(..., "count") and offsets
+    int64[n] its exclusive scan (tr_hits_scan) for the same queries; total (a Python int) sizes the outputs.  Nothing is
+    allocated by the library and nothing is synchronised."""
+    lib = get_scene_tris_module()
+    tri, n, dev = _scene_tris_args(tri, device_index)
+    total = _check_fill(count, offsets, total, n, dev, "triangles")
+    inst, face = _outputs((total,), dev, _I32, _I32)
+    _call(lib.tr_scene_tris_fill, dev, handle, tri.data_ptr(), n, count.data_ptr(), offsets.data_ptr(), total, _ptr_rows(inst),
+          _ptr_rows(face), int(stack_entries))
+    return inst, face
+
+
+def scene_faces_meeting_triangles_native(handle, device_index, tri, stack_entries=0):
+    """(offsets int64[n + 1], instance int32[h], face int32[h]): one count launch, one scan, one host read of the total to size
+    the outputs (as faces_meeting_triangles_native), one fill."""
+    return _count_scan_fill(scene_tris_native, scene_tris_fill_native, (handle, device_index, tri), ("count", stack_entries),
+                            (stack_entries,))

@@ -129,6 +129,25 @@ def _with_columns(fixed, *optional):
     return tuple(fixed) + tuple(column for wanted, column in optional if wanted)
 
 
+def _other_triangles(vertices, faces, chunk, dev):
+    """the faces of another mesh as query triangles: float32 [m, 3, 3] on the GPU `dev` of the acceleration structure or scene
+    that is asked (vertices[faces] gathered there), and the checked chunk size"""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    _on_device(vertices, "vertices", dev, cpu_ok=True)
+    _on_device(faces, "faces", dev, cpu_ok=True)
+    v = _to_device_tensor(vertices, torch.float32, dev)
+    f = _to_device_tensor(faces, torch.int64, dev)
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must have shape [v, 3], got {tuple(v.shape)}")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces must have shape [m, 3], got {tuple(f.shape)}")
+    if f.numel() and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+        raise ValueError(f"faces index outside the {v.shape[0]} vertices")
+    return v[f].contiguous(), chunk
+
+
 class RayMeshIntersector:
     """ray_optix.py:18.  Either `mesh=` or `vertices=` and `faces=` must be provided."""
 
@@ -581,23 +600,7 @@ class RayMeshIntersector:
         return hops.faces_meeting_triangles_native(self.as_wrapper, flat)
 
     def _other_triangles(self, vertices, faces, chunk):
-        """the faces of another mesh as query triangles: float32 [m, 3, 3] on the acceleration structure's GPU (vertices[faces]
-        gathered there), and the checked chunk size"""
-        chunk = int(chunk)
-        if chunk < 1:
-            raise ValueError("chunk must be positive")
-        dev = self.mesh_vertices.device
-        _on_device(vertices, "vertices", dev, cpu_ok=True)
-        _on_device(faces, "faces", dev, cpu_ok=True)
-        v = _to_device_tensor(vertices, torch.float32, dev)
-        f = _to_device_tensor(faces, torch.int64, dev)
-        if v.dim() != 2 or v.shape[1] != 3:
-            raise ValueError(f"vertices must have shape [v, 3], got {tuple(v.shape)}")
-        if f.dim() != 2 or f.shape[1] != 3:
-            raise ValueError(f"faces must have shape [m, 3], got {tuple(f.shape)}")
-        if f.numel() and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
-            raise ValueError(f"faces index outside the {v.shape[0]} vertices")
-        return v[f].contiguous(), chunk
+        return _other_triangles(vertices, faces, chunk, self.mesh_vertices.device)
 
     def mesh_collides(self, vertices, faces, chunk=1 << 20) -> bool:
         """does any face of the other mesh (vertices [v, 3], faces [m, 3]) meet any face of this one (triangles_any's

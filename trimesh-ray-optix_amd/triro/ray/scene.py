@@ -3,7 +3,8 @@
 A scene holds references to RayMeshIntersector members and a list of instances: a member index and a placement, object
 to world, any invertible affine map.  One BVH serves every copy of a member, and moving an object is a commit of twelve
 floats, not a rebuild.  Distances are the world ray's own parameter (an affine map preserves it), so the answer is the
-minimum over the instances of the range query on the transformed ray: csrc/tr_scene.h has the contract.
+minimum over the instances of the range query on the transformed ray: csrc/tr_scene.h has the contract.  Point and triangle
+queries (closest_point, triangles_any, mesh_contacts, ...) walk the members as they are and place what they meet into world space.
 
 Not in the reference (which has one mesh in one coordinate system): what OptiX answers with instance acceleration
 structures."""
@@ -13,8 +14,8 @@ import numpy as np
 import torch
 
 import triro.backend.ops as hops
-from triro.ray.ray_optix import (RayMeshIntersector, _default_device, _flat_queries, _query_bound, _range_rays, _segment_rays,
-                                 _with_columns)
+from triro.ray.ray_optix import (RayMeshIntersector, _default_device, _flat_queries, _other_triangles, _query_bound, _range_rays,
+                                 _segment_rays, _with_columns)
 
 
 def _transforms(transforms) -> np.ndarray:
@@ -213,3 +214,57 @@ class RaySceneIntersector:
         _, distance, _, _ = hops.scene_closest_point_native(self._handle, self.device.index, flat, None, want_closest=False)
         inside = hops.scene_points_any_native(self._handle, self.device.index, flat, direction)
         return torch.where(inside, distance, -distance).reshape(b)
+
+    # -- triangle queries: a mesh against the placed copies (libtriro_scene_tris.so, include/triro_scene_tris.h) -------------
+    def _query_triangles(self, triangles):
+        return _flat_queries(triangles, "triangles", (3, 3), self.device)
+
+    def triangles_any(self, triangles) -> torch.Tensor:
+        """bool[*b]: does any face of any placed copy meet each of the world triangles [*b, 3, 3] -- one launch
+        (tr_scene_tris_any), RayMeshIntersector.triangles_any on the mesh that bakes every placed copy, without baking.  The
+        members' hierarchies are walked as they are; boxes and faces are placed into world space by the scene's own float32
+        chain and tested there by triangles_any's predicate (csrc/tr_tris.h: both triangles have area and the closed triangles
+        share a point, touching included).  A query with a NaN or an infinity, or one without area, meets nothing; a placed
+        face with a non-finite coordinate or without area is never met."""
+        flat, b = self._query_triangles(triangles)
+        return hops.scene_tris_native(self._handle, self.device.index, flat, "any").reshape(b)
+
+    def triangles_count(self, triangles) -> torch.Tensor:
+        """int32[*b]: how many (instance, face) pairs meet each triangle (tr_scene_tris_count); see triangles_any.  Two
+        instances with the same placement count twice."""
+        flat, b = self._query_triangles(triangles)
+        return hops.scene_tris_native(self._handle, self.device.index, flat, "count").reshape(b)
+
+    def faces_meeting_triangles(self, triangles):
+        """(offsets int64[n + 1], instance int32[h], tri_idx int32[h]) for the triangles flattened in order -- the pairs that
+        meet triangle i are rows offsets[i]:offsets[i + 1], ascending by (instance, face index in the member mesh), uncapped.
+        One count launch, one scan, one host read of the total to size the outputs, one fill (two launches)."""
+        flat, _ = self._query_triangles(triangles)
+        return hops.scene_faces_meeting_triangles_native(self._handle, self.device.index, flat)
+
+    def mesh_collides(self, vertices, faces, chunk=1 << 20) -> bool:
+        """does any face of the other mesh (vertices [v, 3], faces [m, 3], world space) meet any face of any placed copy
+        (triangles_any's predicate)?  Host code on triangles_any, `chunk` faces per launch; stops at the first chunk that says
+        yes."""
+        tri, chunk = _other_triangles(vertices, faces, chunk, self.device)
+        for start in range(0, tri.shape[0], chunk):
+            if bool(hops.scene_tris_native(self._handle, self.device.index, tri[start:start + chunk], "any").any()):
+                return True
+        return False
+
+    def mesh_contacts(self, vertices, faces, chunk=1 << 20) -> torch.Tensor:
+        """int64[m, 3]: every triple (face of the other mesh, instance, face of the member) that meets, in lexicographic
+        order -- the contact pairs of a mesh and a scene.  Host code on faces_meeting_triangles, `chunk` faces of the other
+        mesh per count / scan / fill; the result does not depend on `chunk`."""
+        tri, chunk = _other_triangles(vertices, faces, chunk, self.device)
+        found = []
+        for start in range(0, tri.shape[0], chunk):
+            offsets, inst, own = hops.scene_faces_meeting_triangles_native(self._handle, self.device.index, tri[start:start + chunk])
+            rows = torch.arange(own.shape[0], dtype=torch.int64, device=self.device)
+            other = torch.searchsorted(offsets[1:].contiguous(), rows, right=True) + start      # the query each row belongs to
+            found.append(torch.stack((other, inst.long(), own.long()), dim=1))
+        return torch.cat(found) if found else torch.zeros((0, 3), dtype=torch.int64, device=self.device)
+
+    def colliding_instances(self, vertices, faces, chunk=1 << 20) -> torch.Tensor:
+        """int64[c]: the instances the other mesh touches, ascending -- the distinct instances of mesh_contacts' rows."""
+        return torch.unique(self.mesh_contacts(vertices, faces, chunk)[:, 1])
