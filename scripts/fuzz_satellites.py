@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Randomised GPU-vs-brute-force parity sweep of the twelve satellite query libraries (run on the GPU box): the long-run form
+"""Randomised GPU-vs-brute-force parity sweep of the fourteen satellite query libraries (run on the GPU box): the long-run form
 of tests/test_gpu_satellite_sweep.py, with the same generator and the same family table (tests/satellite_sweep.py).  Per
 iteration a fresh handle, every native entry of the family at the drawn knobs, bit for bit against the host brute force, and
 in every second iteration a refit and the same again.  A mismatch prints MISMATCH with the line that reproduces the case and
 the sweep goes on; an exception from a native call ends the run at once -- nothing more is started on a device that has raised.
-usage: python scripts/fuzz_satellites.py [--iters 60] [--seed 1] [--family all]"""
+usage: python scripts/fuzz_satellites.py [--iters 60] [--seed 1] [--family all | a family | several, comma-separated]"""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "trimesh-ray-optix_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "host_sim")]
@@ -14,7 +14,7 @@ import satellite_sweep as S
 import triro.backend.ops as hops
 
 ap = argparse.ArgumentParser(); ap.add_argument("--iters", type=int, default=60); ap.add_argument("--seed", type=int, default=1)
-ap.add_argument("--family", default="all", help="one of " + ", ".join(S.FAMILIES) + " (default: all of them)")
+ap.add_argument("--family", default="all", help="one or several (comma-separated) of the fourteen: " + ", ".join(S.FAMILIES) + " (default: all of them)")
 a = ap.parse_args()
 families = S.FAMILIES if a.family == "all" else tuple(a.family.split(","))
 assert all(f in S.FAMILIES for f in families), families

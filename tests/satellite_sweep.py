@@ -1,5 +1,5 @@
 """Shared by tests/test_satellite_sweep_cpu.py, tests/test_gpu_satellite_sweep.py and scripts/fuzz_satellites.py (not a test
-module): the generator and the family table of the randomised parity sweep of the twelve satellite query libraries.
+module): the generator and the family table of the randomised parity sweep of the fourteen satellite query libraries.
 
 draw(family, seed, iteration) is a deterministic function: a random mesh of one of eight kinds (the kind is iteration % 8, the
 seed decides the parameters only), scaled and shifted, a batch of queries from the generators of the *_cases modules, the
@@ -17,12 +17,16 @@ import scene_cases as SC
 import scene_cross_cases as XC
 import scene_nearest_cases as NN
 import scene_points_cases as SPC
+import scene_tris_cases as ST
+import tri_nearest_cases as TN
 import tris_cases as TC
 import within_cases as WC
 import workloads as W
 
-FAMILIES = ("points", "nearest", "range", "within", "cross", "boxes", "tris", "planes", "scene", "scene_cross", "scene_points", "scene_nearest")
-SCENES = ("scene", "scene_cross", "scene_points", "scene_nearest")
+# (draw() seeds its generator with the family's index: a new family goes to the END, so that the cases of the others stay)
+FAMILIES = ("points", "nearest", "range", "within", "cross", "boxes", "tris", "planes", "scene", "scene_cross", "scene_points", "scene_nearest",
+            "tri_nearest", "scene_tris")
+SCENES = ("scene", "scene_cross", "scene_points", "scene_nearest", "scene_tris")
 KINDS = ("few", "icosphere", "soup", "shells", "displaced", "deep", "flat", "holed")      # (a) .. (h) of the sweep
 CLOSED_KINDS = (1, 3, 4)
 MAX_TRIS, MAX_MEMBER_TRIS, MAX_QUERIES, MAX_INSTANCES = 1500, 400, 700, 70
@@ -180,9 +184,11 @@ def _query_triangles(rng, v, lo, hi, n):
 
 
 def _capacity(family):
-    import boxes_sim, cross_sim, nearest_sim, range_sim, scene_cross_sim, scene_nearest_sim, scene_points_sim, tris_sim, within_sim      # noqa: E401
+    import boxes_sim, cross_sim, nearest_sim, range_sim, scene_cross_sim, scene_nearest_sim, scene_points_sim, scene_tris_sim      # noqa: E401
+    import tri_nearest_sim, tris_sim, within_sim      # noqa: E401
     sims = dict(nearest=nearest_sim, range=range_sim, within=within_sim, cross=cross_sim, boxes=boxes_sim, tris=tris_sim, scene=range_sim,
-                scene_cross=scene_cross_sim, scene_points=scene_points_sim, scene_nearest=scene_nearest_sim)
+                scene_cross=scene_cross_sim, scene_points=scene_points_sim, scene_nearest=scene_nearest_sim, tri_nearest=tri_nearest_sim,
+                scene_tris=scene_tris_sim)
     return sims[family].stack_capacity()
 
 
@@ -211,14 +217,40 @@ def _queries(rng, family, v, lo, hi, n):
     if family in ("range", "cross", "scene", "scene_cross"):
         q["o"], q["d"], q["tmin"], q["tmax"] = _rays(rng, lo, hi, n)
         note = ", no bounds" if q["tmin"] is None else ", per-ray [tmin, tmax]"
+    if family in ("tri_nearest", "scene_tris"):
+        q["tri"], label = _query_triangles(rng, v, lo, hi, n)
+        note = f", query faces of {label}"
+        if family == "tri_nearest":
+            if rng.random() < 0.25:
+                q["md"], note = None, note + ", unbounded"
+            else:
+                q["md"], note = WC.hashed_radii(n, float((hi - lo).max()), seed=int(rng.integers(1 << 20))), note + ", hashed max_distance"
+        # every thirteenth query is invalid (one NaN component, each of the nine in turn): inside live waves and instance loops
+        rows = np.arange(9, n, 13)
+        q["tri"].reshape(n, 9)[rows, rows % 9] = np.nan
     return q, note
 
 
-def _knobs(rng, family):
+def invalid_queries(case):
+    """[n] bool: the query triangles of the two triangle families that hold a NaN"""
+    return ~np.isfinite(case.q["tri"]).all(axis=(1, 2))
+
+
+SCHEDULED_LIMITS = (0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, None)      # (None: the capacity)
+
+
+def _knobs(rng, family, seed, iteration):
     if family == "points":
         return {}
     if family == "planes":
         return {"frontier_entries": int(rng.choice(PC.FRONTIERS))}
+    if family in ("tri_nearest", "scene_tris"):
+        # the nearest-face walk pushes a far child only where the bound so far does not cull it, and independent draws left
+        # too few iterations at a limit a lane can overflow: the limits come by a schedule of the (seed, family) over 16
+        # iterations, as the batch sizes do, so that every pass of 16 holds 14 at a limit of 1, 2 or 3
+        slot = np.random.default_rng((seed, FAMILIES.index(family), 0, 0)).permutation(len(SCHEDULED_LIMITS))[iteration % len(SCHEDULED_LIMITS)]
+        limit = SCHEDULED_LIMITS[slot]
+        return {"stack_entries": _capacity(family) if limit is None else limit}
     # (1, 2 and 3 entries are the ones a lane can overflow: drawn more often than the two that cannot lose a push)
     return {"stack_entries": int(rng.choice([0, 1, 2, 3, _capacity(family)], p=[0.1, 0.3, 0.25, 0.25, 0.1]))}
 
@@ -233,7 +265,7 @@ def draw(family, seed, iteration):
         v, f, v2, label = draw_mesh(rng, kind, iteration, refit=refits(iteration))
         lo, hi = finite_box(v)
         q, note = _queries(rng, family, v, lo, hi, n)
-        knobs = _knobs(rng, family)
+        knobs = _knobs(rng, family, seed, iteration)
         line = head + f"{label}, {len(f)} triangles, batch {n}{note}, {knobs}, refit {v2 is not None}"
         return Case(family=family, seed=seed, iteration=iteration, kind=kind, v=v, f=f, v2=v2, n=n, q=q, knobs=knobs, line=line)
     # a scene: 1 to 4 members (the first of this iteration's kind), 1 to 70 instances placed by general affine maps
@@ -266,7 +298,7 @@ def draw(family, seed, iteration):
     lo, hi = np.min([b[0] for b in boxes], 0), np.max([b[1] for b in boxes], 0)
     world = np.concatenate([np.stack(b) for b in boxes]).astype(F32)
     q, note = _queries(rng, family, world, lo, hi, n)
-    knobs = _knobs(rng, family)
+    knobs = _knobs(rng, family, seed, iteration)
     knobs["order"] = rng.permutation(ninst).astype(np.int32)           # the order the host walk visits the instances in
     refit_member, v2 = None, None
     if refits(iteration):
@@ -389,7 +421,8 @@ def host_trees_refitted(case, trees):
 # ---- the family table ---------------------------------------------------------------------------------------------------
 # brute(case, geometry) -> want;  walk(case, trees, geometry) -> (got, lost [n] bool or None: the walk does not report it);
 # native(case, handle, device, want) -> got (every native entry of the family once; points: compares inside check_all);
-# same(got, want, what): the family's comparator;  hits(want) -> [n] bool or count per query: what the lists or masks hold
+# same(got, want, what): the family's comparator;  hits(want) -> [n] bool or count per query: what the lists or masks hold;
+# no_result(case, got, what), the two triangle families: the queries made invalid by a NaN came back as "no result"
 def _oracle(geom):
     from oracle.oracle import OracleIntersector
     return OracleIntersector(geom[0], geom[1], 1)
@@ -466,6 +499,16 @@ def _scene_points_walk(c, trees, geom=None):
     return got, lost >= 0
 
 
+def _split(got, k):
+    """a walk's (k results..., lost) -> ((k results), lost)"""
+    return got[:k], got[k]
+
+
+def _scene_tris_no_result(c, got, what):
+    bad = invalid_queries(c)
+    assert not np.asarray(got.any)[bad].any() and not np.asarray(got.count)[bad].any(), f"{what}: an invalid query has rows"
+
+
 def _sim(name):
     import importlib
     return importlib.import_module(name + "_sim")
@@ -539,6 +582,22 @@ TABLE = {
         same=NN.assert_same,
         native=lambda c, s, dev, geom: _gpu("scene_nearest").native(s, c.q["p"], c.q["md"], dev, stack_entries=c.knobs["stack_entries"]),
         hits=lambda w: w.tri >= 0),
+    "tri_nearest": dict(
+        brute=lambda c, g: _sim("tri_nearest").brute(g[0], g[1], c.q["tri"], c.q["md"]),
+        walk=lambda c, B, geom=None: _split(_sim("tri_nearest").walk(B, c.q["tri"], c.q["md"], c.knobs["stack_entries"], want_lost=True), 4),
+        same=TN.assert_same,
+        native=lambda c, r, dev, geom: _gpu("tri_nearest").native(r, c.q["tri"], dev, c.q["md"], stack_entries=c.knobs["stack_entries"]),
+        hits=lambda w: w[0] >= 0,
+        no_result=lambda c, got, what: TN.check_no_result(got, invalid_queries(c), what + ": an invalid query has a result")),
+    "scene_tris": dict(
+        brute=lambda c, mem: _sim("scene_tris").brute(mem, c.mesh_of, c.M, c.q["tri"]),
+        walk=lambda c, trees, geom=None: _sim("scene_tris").walk(trees, c.mesh_of, c.M, c.q["tri"], c.knobs["stack_entries"], order=c.knobs["order"],
+                                                                 want_lost=True),
+        same=ST.assert_same,
+        # (the three C entries themselves, between poisoned guard rows, every row inside checked: no binding to wrap)
+        native=lambda c, s, dev, geom: _gpu("scene_tris").native(s, c.q["tri"], dev, stack_entries=c.knobs["stack_entries"]),
+        hits=lambda w: w.count,
+        no_result=_scene_tris_no_result),
 }
 assert tuple(TABLE) == FAMILIES
 
@@ -546,7 +605,7 @@ assert tuple(TABLE) == FAMILIES
 def natives():
     """the union of the native entry points the families' GPU modules wrap: every call of one is followed by assert_written"""
     names = ["contains_points_native", "closest_point_native", "range_any_native", "range_closest_native", "scene_any_native",
-             "scene_closest_native", "scene_closest_point_native"]
+             "scene_closest_native", "scene_closest_point_native", "triangles_nearest_native"]
     for name in ("within", "cross", "boxes", "tris", "planes", "scene_cross", "scene_points"):
         names += [x for x in _gpu(name).NATIVES if x not in names]
     return tuple(names)
@@ -566,7 +625,10 @@ def run_host(case, walk=None):
         geom = geometry(case, refitted)
         want = row["brute"](case, geom)
         got, lost = walk(case, trees, geom)
-        row["same"](got, want, f"{case.line} [host walk{', after the refit' if refitted else ''}]")
+        what = f"{case.line} [host walk{', after the refit' if refitted else ''}]"
+        row["same"](got, want, what)
+        if "no_result" in row:
+            row["no_result"](case, got, what)
         out.append((want, lost))
     return out
 
@@ -593,4 +655,7 @@ def run_device(case, device):
         geom = geometry(case, refitted)
         want = row["brute"](case, geom)
         got = row["native"](case, handle, device, geom)
-        row["same"](got, want, f"{case.line} [native{', after the refit' if refitted else ''}]")
+        what = f"{case.line} [native{', after the refit' if refitted else ''}]"
+        row["same"](got, want, what)
+        if "no_result" in row:
+            row["no_result"](case, got, what)

@@ -65,12 +65,13 @@ def c(device):
     c.packed = torch.full((3, 3), -1, dtype=i32, device=device)
     c.outs = lambda: (torch.zeros(3, dtype=b_, device=device), torch.zeros(3, dtype=b_, device=device), torch.zeros(3, dtype=i32, device=device),
                       torch.zeros((3, 3), dtype=f32, device=device), torch.zeros((3, 2), dtype=f32, device=device))
-    # the seven fills: (function, the arguments before (count, offsets, total))
+    # the eight fills: (function, the arguments before (count, offsets, total))
     c.fills = {"within": ("within_fill_native", (c.aw, x.p, 0.5)), "boxes": ("boxes_fill_native", (c.aw, x.lo, x.hi)),
                "tris": ("tris_fill_native", (c.aw, x.tri)), "planes": ("planes_fill_native", (c.aw, x.p, x.nrm)),
                "cross": ("cross_fill_native", (c.aw, x.o, x.d, None, None)),
                "scene_cross": ("scene_cross_fill_native", (c.sh, c.di, x.o, x.d, None, None)),
-               "scene_points": ("scene_points_fill_native", (c.sh, c.di, x.p, c.direction))}
+               "scene_points": ("scene_points_fill_native", (c.sh, c.di, x.p, c.direction)),
+               "scene_tris": ("scene_tris_fill_native", (c.sh, c.di, x.tri))}
     # the four functions that take `outs`: outs -> the call
     c.with_outs = {"intersects_closest": lambda outs: hops().intersects_closest(c.aw, x.o, x.d, outs=outs),
                    "closest_from_slots": lambda outs: hops().closest_from_slots(c.aw, x.o, x.d, c.slots, outs=outs),
@@ -259,6 +260,44 @@ REJECTED = [
     (lambda c: c.s.signed_distance(X(c).p.cpu()), V, "points must reside on a GPU"),
     (lambda c: c.s.closest_point(X(c).p[:, :2]), V, r"points must have shape \[\*b, 3\]"),
     (lambda c: c.s.closest_point(X(c).p, max_distance=X(c).r[:2]), V, "max_distance of shape .* does not broadcast"),
+    # (new rows go to the end: the ids of the rows above hold their index)
+    # RayMeshIntersector.triangles_nearest and mesh_distance, and the native entry under them
+    (lambda c: c.r.triangles_nearest(X(c).tri.cpu()), V, "triangles must reside on a GPU"),
+    (lambda c: c.r.triangles_nearest(X(c).tri[:, :2]), V, r"triangles must have shape \[\*b, 3, 3\]"),
+    (lambda c: c.r.triangles_nearest(X(c).tri.reshape(-1, 9)), V, r"triangles must have shape \[\*b, 3, 3\]"),
+    (lambda c: c.r.triangles_nearest(X(c).tri, X(c).r[:2]), V, "max_distance of shape .* does not broadcast"),
+    (lambda c: c.r.triangles_nearest(X(c).tri, [0.5, 0.5]), V, "max_distance of shape .* does not broadcast"),
+    (lambda c: c.r.mesh_distance(VERTICES, FACES, chunk=0), V, "chunk must be positive"),
+    (lambda c: c.r.mesh_distance(VERTICES[:, :2], FACES), V, r"vertices must have shape \[v, 3\]"),
+    (lambda c: c.r.mesh_distance(VERTICES, FACES[:, :2]), V, r"faces must have shape \[m, 3\]"),
+    (lambda c: c.r.mesh_distance(VERTICES, FACES + 2), V, "faces index outside the 4 vertices"),
+    (lambda c: c.r.mesh_distance(VERTICES, FACES - 1), V, "faces index outside the 4 vertices"),
+    (lambda c: hops().triangles_nearest_native(c.unbuilt, X(c).tri), R, "has not been built"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri.cpu()), V, "triangles must be a float32 GPU tensor"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri.double()), V, "triangles must be a float32 GPU tensor"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri.reshape(-1, 3)), V, r"triangles must be .* \[n, 3, 3\]"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri, X(c).r[:2]), V, "max_distance must be a number or a contiguous float32"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri, X(c).r.cpu()), V, "max_distance must be a number or a contiguous float32"),
+    (lambda c: hops().triangles_nearest_native(c.aw, X(c).tri, X(c).r.double()), V, "max_distance must be a number or a contiguous float32"),
+    # RaySceneIntersector: triangles and another mesh go through the rules of the mesh class, on the scene's device
+    (lambda c: c.s.triangles_any(X(c).tri.cpu()), V, "triangles must reside on a GPU"),
+    (lambda c: c.s.triangles_count(X(c).tri.reshape(-1, 3)), V, r"triangles must have shape \[\*b, 3, 3\]"),
+    (lambda c: c.s.faces_meeting_triangles(X(c).tri[:, :2]), V, r"triangles must have shape \[\*b, 3, 3\]"),
+    (lambda c: c.s.mesh_collides(VERTICES, FACES, chunk=0), V, "chunk must be positive"),
+    (lambda c: c.s.colliding_instances(VERTICES, FACES, chunk=-1), V, "chunk must be positive"),
+    (lambda c: c.s.mesh_contacts(VERTICES[:, :2], FACES), V, r"vertices must have shape \[v, 3\]"),
+    (lambda c: c.s.mesh_collides(VERTICES, FACES[:, :2]), V, r"faces must have shape \[m, 3\]"),
+    (lambda c: c.s.mesh_contacts(VERTICES, FACES + 2), V, "faces index outside the 4 vertices"),
+    (lambda c: c.s.colliding_instances(VERTICES, FACES - 1), V, "faces index outside the 4 vertices"),
+    (lambda c: hops().scene_tris_native(c.sh, c.di, X(c).tri.cpu()), V, "triangles must be a float32 GPU tensor"),
+    (lambda c: hops().scene_tris_native(c.sh, c.di, X(c).tri.double(), "count"), V, "triangles must be a float32 GPU tensor"),
+    (lambda c: hops().scene_faces_meeting_triangles_native(c.sh, c.di, X(c).tri.reshape(-1, 3)), V, r"triangles must be .* \[n, 3, 3\]"),
+    (lambda c: hops().scene_tris_fill_native(c.sh, c.di, X(c).tri[:, :2], c.count, c.offsets, 0), V, r"triangles must be .* \[n, 3, 3\]"),
+    (lambda c: hops().scene_tris_native(c.sh, c.di, X(c).tri, "list"), V, "query must be 'any' or 'count'"),
+    (lambda c: hops().scene_tris_native(c.sh, c.di, X(c).tri, None), V, "query must be 'any' or 'count'"),
+    (lambda c: hops().scene_tris_native(c.sh, c.di + 1, X(c).tri), V, "triangles are on .* but the scene lives on"),
+    (lambda c: hops().scene_tris_fill_native(c.sh, c.di + 1, X(c).tri, c.count, c.offsets, 0), V, "triangles are on .* but the scene lives on"),
+    (lambda c: hops().scene_tris_native(None, c.di, X(c).tri), V, "scene == NULL"),      # (a scene is built or it has no handle)
 ]
 
 
@@ -288,7 +327,7 @@ def test_rejected_outs(c, name, bad):
 
 
 @pytest.mark.parametrize("bad", ("count dtype", "count length", "offsets dtype", "offsets length", "offsets contiguity", "total"))
-@pytest.mark.parametrize("family", ("within", "boxes", "tris", "planes", "cross", "scene_cross", "scene_points"))
+@pytest.mark.parametrize("family", ("within", "boxes", "tris", "planes", "cross", "scene_cross", "scene_points", "scene_tris"))
 def test_rejected_fill_arguments(c, family, bad):
     """every fill takes count int32[n] and offsets int64[n], contiguous on the queries' device, and a total that is not negative"""
     name, args = c.fills[family]
@@ -343,6 +382,18 @@ def test_rejected_tensors_of_another_gpu(c):
         (lambda: c.r.segments_any(x.o, F(x.p1)), "p1 is on .* but the acceleration structure lives on"),
         (lambda: c.s.intersects_any(F(x.o), F(x.d)), "origins is on"),
         (lambda: c.s.contains_points(F(x.p)), "points .* on"),
+        (lambda: c.r.triangles_nearest(F(x.tri)), "triangles is on .* but the acceleration structure lives on"),
+        (lambda: c.r.triangles_nearest(x.tri, F(x.r)), "max_distance is on .* but the acceleration structure lives on"),
+        (lambda: c.r.mesh_distance(F(c.r.mesh_vertices), FACES), "vertices is on .* but the acceleration structure lives on"),
+        (lambda: hops().triangles_nearest_native(c.aw, x.tri, F(x.r)), "max_distance must be a number or"),
+        (lambda: c.s.triangles_any(F(x.tri)), "triangles is on"),
+        (lambda: c.s.triangles_count(F(x.tri)), "triangles is on"),
+        (lambda: c.s.faces_meeting_triangles(F(x.tri)), "triangles is on"),
+        (lambda: c.s.mesh_collides(F(c.r.mesh_vertices), FACES), "vertices is on"),
+        (lambda: c.s.mesh_contacts(c.r.mesh_vertices, F(c.r.mesh_faces)), "faces is on"),
+        (lambda: c.s.colliding_instances(F(c.r.mesh_vertices), FACES), "vertices is on"),
+        (lambda: hops().scene_tris_native(c.sh, c.di, F(x.tri)), "triangles are on .* but the scene lives on"),
+        (lambda: hops().scene_tris_fill_native(c.sh, c.di, x.tri, F(c.count), c.offsets, 0), "count must be"),
     ]
     for call, fragment in rows:
         with pytest.raises(ValueError, match=fragment):
@@ -418,6 +469,9 @@ MESH_QUERIES = [
     ("triangles_any", lambda c, x: c.r.triangles_any(x.tri), "bB"),
     ("triangles_count", lambda c, x: c.r.triangles_count(x.tri), "iB"),
     ("faces_meeting_triangles", lambda c, x: c.r.faces_meeting_triangles(x.tri), "lN1 iH"),
+    ("triangles_nearest", lambda c, x: c.r.triangles_nearest(x.tri), "iB fB fB3 fB3"),
+    ("triangles_nearest number", lambda c, x: c.r.triangles_nearest(x.tri, 0.5), "iB fB fB3 fB3"),
+    ("triangles_nearest tensor", lambda c, x: c.r.triangles_nearest(x.tri, max_distance=x.r), "iB fB fB3 fB3"),
     ("signed_distance", lambda c, x: c.r.signed_distance(x.p), "fB"),
     ("intersects_any_range", lambda c, x: c.r.intersects_any_range(x.o, x.d), "bB"),
     ("intersects_any_range bounds", lambda c, x: c.r.intersects_any_range(x.o, x.d, x.tmin, x.tmax), "bB"),
@@ -452,6 +506,9 @@ SCENE_QUERIES = [
     ("closest_point number", lambda c, x: c.s.closest_point(x.p, max_distance=0.5), "fB3 fB iB iB"),
     ("closest_point tensor", lambda c, x: c.s.closest_point(x.p, max_distance=x.r), "fB3 fB iB iB"),
     ("signed_distance", lambda c, x: c.s.signed_distance(x.p), "fB"),
+    ("triangles_any", lambda c, x: c.s.triangles_any(x.tri), "bB"),
+    ("triangles_count", lambda c, x: c.s.triangles_count(x.tri), "iB"),
+    ("faces_meeting_triangles", lambda c, x: c.s.faces_meeting_triangles(x.tri), "lN1 iH iH"),
 ]
 
 
@@ -494,6 +551,25 @@ def test_mesh_queries_return_the_documented_shapes(c, bs):
 def test_scene_queries_return_the_documented_shapes(c, bs):
     for name, call, outputs in SCENE_QUERIES:
         check_shapes(name, call(c, c.x[bs]), outputs, c.x[bs], c.dev)
+
+
+@pytest.mark.parametrize("bs", BATCHES, ids=str)
+def test_mesh_against_mesh_queries_return_the_documented_shapes(c, bs):
+    """the other mesh has one face per query triangle of the batch shape (none for (0,)): what comes back does not have the
+    batch shape but scalars and rows"""
+    x = c.x[bs]
+    v, f = x.tri.reshape(3 * x.n, 3), torch.arange(3 * x.n, device=c.dev).reshape(x.n, 3)
+    d, other, own, on_other, on_self = c.r.mesh_distance(v, f)
+    assert all(t.device == c.dev for t in (d, other, own, on_other, on_self))
+    assert d.dtype == f32 and d.shape == () and other.dtype == own.dtype == i64 and other.shape == own.shape == ()
+    assert on_other.dtype == on_self.dtype == f32 and on_other.shape == on_self.shape == (3,)
+    assert (int(other) == -1 and int(own) == -1 and bool(torch.isinf(d))) if x.n == 0 else (0 <= int(other) < x.n and 0 <= int(own) < len(FACES))
+    for r in (c.r, c.s):
+        assert isinstance(r.mesh_collides(v, f), bool) and (x.n > 0 or not r.mesh_collides(v, f))
+    rows, hit = c.s.mesh_contacts(v, f), c.s.colliding_instances(v, f)
+    assert rows.dtype == hit.dtype == i64 and rows.device == hit.device == c.dev and rows.dim() == 2 and rows.shape[1] == 3 and hit.dim() == 1
+    assert x.n > 0 or (rows.shape[0] == 0 and hit.shape[0] == 0)
+    assert torch.equal(hit, torch.unique(rows[:, 1]))
 
 
 def test_the_optional_columns_come_in_their_order(c):
@@ -547,6 +623,8 @@ ARRAY_LIKE = [
     ("mesh_collides", lambda c, K, x: torch.tensor(c.r.mesh_collides(K(x.tri.reshape(-1, 3)), [[0, 1, 2], [3, 4, 5], [6, 7, 8]]))),
     ("mesh_contacts", lambda c, K, x: c.r.mesh_contacts(K(x.tri.reshape(-1, 3)), np.arange(9).reshape(3, 3))),
     ("signed_distance", lambda c, K, x: c.r.signed_distance(K(x.p))),
+    ("triangles_nearest", lambda c, K, x: c.r.triangles_nearest(K(x.tri), K(x.r))),
+    ("mesh_distance", lambda c, K, x: c.r.mesh_distance(K(x.tri.reshape(-1, 3)), np.arange(9).reshape(3, 3))),
     ("intersects_any_range", lambda c, K, x: c.r.intersects_any_range(K(x.o), K(x.d), K(x.tmin), K(x.tmax))),
     ("intersects_closest_range", lambda c, K, x: c.r.intersects_closest_range(K(x.o), K(x.d), 0.5, K(x.tmax))),
     ("intersects_count_range", lambda c, K, x: c.r.intersects_count_range(K(x.o), x.d, K(x.tmin))),
@@ -568,6 +646,12 @@ ARRAY_LIKE = [
     ("scene.containing_instances", lambda c, K, x: c.s.containing_instances(K(x.p), K(c.direction))),
     ("scene.closest_point", lambda c, K, x: c.s.closest_point(K(x.p), max_distance=K(x.r))),
     ("scene.signed_distance", lambda c, K, x: c.s.signed_distance(K(x.p), K(c.direction))),
+    ("scene.triangles_any", lambda c, K, x: c.s.triangles_any(K(x.tri))),
+    ("scene.triangles_count", lambda c, K, x: c.s.triangles_count(K(x.tri))),
+    ("scene.faces_meeting_triangles", lambda c, K, x: c.s.faces_meeting_triangles(K(x.tri))),
+    ("scene.mesh_collides", lambda c, K, x: torch.tensor(c.s.mesh_collides(K(x.tri.reshape(-1, 3)), [[0, 1, 2], [3, 4, 5], [6, 7, 8]]))),
+    ("scene.mesh_contacts", lambda c, K, x: c.s.mesh_contacts(K(x.tri.reshape(-1, 3)), np.arange(9).reshape(3, 3))),
+    ("scene.colliding_instances", lambda c, K, x: c.s.colliding_instances(K(x.tri.reshape(-1, 3)), np.arange(9).reshape(3, 3))),
 ]
 CONVERSIONS = {"list": lambda t: t.cpu().tolist(), "float64 array": lambda t: t.cpu().numpy().astype(np.float64),
                "float64 tensor on the GPU": lambda t: t.double(), "float32 array": lambda t: t.cpu().numpy()}

@@ -11,9 +11,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("rccl", "points", "nearest", "range", "scene", "within", "cross", "scene_cross", "scene_points", "boxes", "tris", "planes",
-        "scene_nearest")
+        "scene_nearest", "tri_nearest", "scene_tris")
 VERSIONED = tuple(k for k in KEYS if k != "rccl")          # libtriro_rccl.so has no version symbol
-ON_THE_SCENE = ("scene_cross", "scene_points", "scene_nearest")      # their handles are libtriro_scene.so's: it loads first
+ON_THE_SCENE = ("scene_cross", "scene_points", "scene_nearest", "scene_tris")      # their handles are libtriro_scene.so's: it loads first
 
 _vp, _int = ctypes.c_void_p, ctypes.c_int
 # what get_rccl_module binds (include/triro_rccl.h), written out here so that the check does not depend on the table it checks
